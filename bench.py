@@ -316,6 +316,37 @@ def condense(o, wall_s):
     return d
 
 
+def _pick(d, keys):
+    return {k: d[k] for k in keys if k in d}
+
+
+def result_line(out):
+    """The printed JSON line: the run's own record in full, the side runs that the default single-GPU run appends (other_configs,
+    reference_precision, next_rows) cut to their headline numbers.  In full they put the line at ~20 KB, more than the benchmark driver
+    takes in of a run's output (BENCH_r06.json: rc 0, no parsed result); --details-json FILE writes the complete record."""
+    line = dict(out)
+    if "other_configs" in out:
+        line["other_configs"] = [_pick(c, ("baseline_config", "value", "ms_per_step", "bound", "frac", "error")) for c in out["other_configs"]]
+    if "reference_precision" in out:
+        rp = out["reference_precision"]
+        line["reference_precision"] = _pick(rp, ("dtype", "value", "ms_per_step", "f32_over_f64", "error"))
+        if isinstance(rp.get("other_configs"), list):
+            line["reference_precision"]["other_configs"] = [_pick(c, ("baseline_config", "value", "ms_per_step", "f32_over_f64", "error"))
+                                                            for c in rp["other_configs"]]
+    if "next_rows" in out:
+        line["next_rows"] = {k: _pick(r, ("ms", "us_resident_block", "k_found", "k_injected")) if k != "error" else r
+                             for k, r in out["next_rows"].items()}
+    return line
+
+
+def emit(args, out):
+    """Rank 0's output: the complete record to --details-json FILE (if given), ONE JSON line on stdout."""
+    if args.details_json:
+        with open(args.details_json, "w") as f:
+            json.dump(out, f)
+    print(json.dumps(result_line(out)))
+
+
 FP64_VECTOR_PEAK_TFLOPS = 78.6      # MI355X data sheet, FP64 vector (256 CUs x 4 SIMDs x 16 lanes x 2 flop x 2.4 GHz); SURVEY App. A plans with 79
 
 
@@ -742,10 +773,18 @@ def main():
                     help="PROJECTION, not a measurement: on this one GPU, time every rank's slice of an N-rank job (the Doppler slices "
                          "ShardedSearch would cut) one after the other and report the slowest slice, per-slice roofline and exchange bytes")
     ap.add_argument("--dry-bins", type=int, default=8, help="--dry-run-cpu: Doppler bins of the miniature grid (fewer than ranks leaves ranks without a slice)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned: every job's merged peak records [epochs, items] "
+                         "as float64 DIR/<job>_metric.npy, <job>_code_index.npy, <job>_doppler_index.npy (at most 64 MB in all)")
+    ap.add_argument("--details-json", default="", metavar="FILE",
+                    help="also write the complete record to FILE: the printed line cuts the side runs of the default run (other_configs, "
+                         "reference_precision, next_rows) to their headline numbers")
     ap.add_argument("--dry-run-cpu", default="", metavar="FILE.py:FUNCTION",
                     help="NOT A MEASUREMENT: run the N-rank launch path on CPU tensors over gloo with FUNCTION(name, x, items, dopplers, blocks) "
                          "-> peaks as the per-rank compute (tests pass an oracle-backed stand-in); no GPU is touched")
     args = ap.parse_args()
+    if args.dump_outputs and args.emulate_ranks:
+        ap.error("--dump-outputs: --emulate-ranks times slices one after the other, there is no step output to dump")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -763,7 +802,7 @@ def main():
         env = {"world": world, "rank": rank, "local_rank": local_rank, "use_dist": use_dist, "dev": torch.device("cpu")}
         out = run_dry(args, env, getattr(mod, fname))
         if rank == 0:
-            print(json.dumps(out))
+            emit(args, out)
         if use_dist:
             dist.destroy_process_group()
         return
@@ -779,7 +818,7 @@ def main():
     if args.emulate_ranks:
         out = emulate_ranks(args, env)
         if rank == 0:
-            print(json.dumps(out))
+            emit(args, out)
         return
 
     t_start = time.perf_counter()
@@ -795,6 +834,7 @@ def main():
             a = argparse.Namespace(**vars(args))
             a.config, a.epochs, a.steps, a.warmup, a.sustained_s, a.preroll_s = k, 0, 5, 1, 1.0, 0.2
             a.no_cpu_baseline = a.no_latency = True
+            a.dump_outputs = ""                          # the dump is the headline configuration's
             t1 = time.perf_counter()
             try:
                 others.append(condense(run(a, env), time.perf_counter() - t1))
@@ -824,7 +864,7 @@ def main():
         out["roofline"]["ab"] = ab
         out["bench_wall_s"] = time.perf_counter() - t_start
     if rank == 0:
-        print(json.dumps(out))
+        emit(args, out)
     if use_dist:
         dist.destroy_process_group()
 
@@ -857,7 +897,8 @@ def build_jobs(cfg, E_total, dev, distinct=0):
 
 def make_run_steps(lanes, jobs):
     """k independent steps, alternating between `lanes` = [(context factory, ShardedSearch)].  With N > 1 the all-gather of step i
-    runs under the local compute of step i+1 (asynchronous collective, merge deferred by one step)."""
+    runs under the local compute of step i+1 (asynchronous collective, merge deferred by one step).  Returns the merged records of
+    step k-1 (the last one queued)."""
     def run_steps(k):
         pend = [None] * len(lanes)
         out = None
@@ -868,12 +909,42 @@ def make_run_steps(lanes, jobs):
                 if pend[i % len(lanes)] is not None:                          # its kernels cover the previous exchange
                     out = pend[i % len(lanes)].wait()
                 pend[i % len(lanes)] = nxt
-        for (ctx, _), p in zip(lanes, pend):
+        for j, ((ctx, _), p) in enumerate(zip(lanes, pend)):
             if p is not None:
                 with ctx():
-                    out = p.wait()
+                    r = p.wait()
+                if j == (k - 1) % len(lanes):
+                    out = r
         return out
     return run_steps
+
+
+DUMP_LIMIT_BYTES = 60 * 10**6          # array data; with the .npy headers and epoch numbers still under 64 MB (decimal or binary)
+DUMP_FIELDS = (("metric", "metric"), ("idx", "code_index"), ("d_index", "doppler_index"))
+
+
+def host_records(merged):
+    """Merged peak tensors [epochs, items, 2] (float64 words of gacq_peak records) -> host structured arrays [epochs, items]."""
+    from gnss_dsp_tools_amd import acquire
+    return [np.ascontiguousarray(m.cpu().numpy()).view(acquire.PEAK_DTYPE).reshape(m.shape[0], m.shape[1]) for m in merged]
+
+
+def dump_outputs(path, jobs, recs):
+    """--dump-outputs DIR: what a caller of the timed path receives from one step -- every job's merged peak records -- one float64
+    array [epochs, items] per record field: DIR/<job>_metric.npy, <job>_code_index.npy (code-phase lag of the peak), <job>_doppler_index.npy
+    (bin of the job's Doppler grid, -1 = nothing found).  Above DUMP_LIMIT_BYTES in all, every job keeps the same fixed, seeded sample
+    of epochs, whose numbers go to <job>_epoch.npy."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(r.size * len(DUMP_FIELDS) * 8 for r in recs)
+    for job, r in zip(jobs, recs):
+        label = job["label"]
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, r.shape[0] * DUMP_LIMIT_BYTES // total)
+            epochs = np.sort(np.random.default_rng(0).choice(r.shape[0], keep, replace=False))
+            r = r[epochs]
+            np.save(os.path.join(path, "%s_epoch.npy" % label), epochs.astype(np.float64))
+        for field, name in DUMP_FIELDS:
+            np.save(os.path.join(path, "%s_%s.npy" % (label, name)), np.ascontiguousarray(r[field], dtype=np.float64))
 
 
 def make_timed(run_steps, dev, use_dist):
@@ -969,6 +1040,8 @@ def run_dry(args, env, local_fn):
     timed = make_timed(run_steps, dev, env["use_dist"])
     run_steps(args.warmup)
     merged, dt = timed(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, jobs, host_records(merged))
     shards_seen = 1
     if not sh._solo():
         shards_seen, merged = shard_census(sh, jobs, world, dev)
@@ -1056,6 +1129,7 @@ def run(args, env):
         preroll["seconds"] = time.perf_counter() - t0
     run_steps(args.warmup)
     merged, dt = timed(args.steps)
+    dumped = host_records(merged) if (args.dump_outputs and rank == 0) else None      # before any later step: the timed path's own output
     one_lane = None
     if len(lanes) > 1:
         # the same K steps with ONE step in flight (lane 0 only), same process, right after the timed region: what the second step in
@@ -1434,6 +1508,8 @@ def run(args, env):
             out["cpu_baseline"] = None
     else:
         out = None
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, jobs, dumped)
     torch.cuda.synchronize(dev)
     for _, e2, _ in lanes:
         e2.close()
