@@ -8,8 +8,11 @@
 // satellite).  The tracking loops themselves (FLL/PLL/DLL feedback, track-gps-l1.py:33-94) are sequential and stay on the host.
 //
 // The reference advances its phases by repeated fp64 addition (cp = (cp+incr) % L); here sample i uses the closed form
-// floor(cp0 + incr*i) mod L.  The two differ only when the accumulated rounding (~1e-11 chips over a block) straddles a chip
-// boundary, i.e. with probability ~1e-8 per correlator call; tests/test_tracking.py holds the result to 1e-5 of the reference.
+// floor(fma(incr, i, cp0)) mod L -- one rounding of the exact phase (and likewise for bp, bp6; 12*incr is rounded first).  The two
+// differ only when the accumulated rounding (~1e-11 chips over a block) straddles a chip boundary.  With decimal rates and start
+// phases the exact phase can land on a boundary, and then the single rounding matters: cp0 + incr*i rounded twice (numpy's closed
+// form) already disagrees with the reference on one of its golden cases, the fused form does not.  tests/test_next_rows_edges.py holds the
+// result to fp64 round-off of oracle/tracking_oracle.correlate_many, which forms the phases the same way.
 #include "gacq_common.h"
 #include "gacq_fft64.h"
 
@@ -46,18 +49,18 @@ __global__ __launch_bounds__(kTrBlock) void correlate_partial_kernel(const float
     const long i = i0 + (long)j * kTrBlock;
     if (i < n) {
       const double di = (double)i;
-      const double pos = sp.cp0 + __dmul_rn(sp.incr, di);
+      const double pos = fma(sp.incr, di, sp.cp0);
       // floor(pos) mod L without a 64-bit division: the quotient from an fp64 product can be off by one, fixed up by one compare each way
       long idx = (long)floor(pos) - (long)floor(pos * inv_l) * L;
       if (idx < 0) idx += L;
       if (idx >= L) idx -= L;
       float w = sp.chips[idx] ? -1.f : 1.f;                          // 1.0 - 2.0*c[int(cp)]
       if (kind != 0) {
-        const long b1 = (long)floor(sp.bp0 + __dmul_rn(2.0 * sp.incr, di)) & 1;        // int(bp), bp = (bp + 2 incr) % 2
+        const long b1 = (long)floor(fma(2.0 * sp.incr, di, sp.bp0)) & 1;               // int(bp), bp = (bp + 2 incr) % 2
         if (kind == 1) {
           w *= b1 ? -1.f : 1.f;                                                        // boc11 = [1, -1]
         } else if (kind == 2 || kind == 3) {
-          const long b6 = (long)floor(sp.bp60 + __dmul_rn(12.0 * sp.incr, di)) & 1;    // int(bp6)
+          const long b6 = (long)floor(fma(12.0 * sp.incr, di, sp.bp60)) & 1;           // int(bp6)
           const float s1 = b1 ? -1.f : 1.f, s6 = b6 ? -1.f : 1.f;
           if (kind == 2) w *= 0.953463f * s1 + 0.301511f * s6;                         // CBOC
           else w *= ((kTmbocMask >> (idx % 33)) & 1ull) ? s6 : s1;                     // TMBOC: u = int(cp % 33)

@@ -30,13 +30,19 @@ def mix_fixed_point(x, f, p=0.0):
     return (x * _TABLE[(ph >> 50) & (NT - 1)]).astype(x.dtype if np.iscomplexobj(x) else np.complex128)
 
 
-def condition(x, fs, coffset, sig, ms_pad):
-    """Carrier wipe-off, low-pass and resample to the signal's internal rate; returns ms_pad ms of complex128."""
-    x = mix_fixed_point(x, -coffset / fs, 0)
+def condition(x, fs, coffset, sig, ms_pad, ntaps=161):
+    """Carrier wipe-off, low-pass and resample to the signal's internal rate; returns ms_pad ms of complex128.
+    ntaps: the filter length (the reference's is 161; other lengths check the device's generic FIR)."""
     per_ms = int(round(sig.fs * 0.001))
-    fsr = sig.fs / fs
-    h = scipy.signal.firwin(161, sig.fir_cutoff / (fs / 2), window='hann')
+    return condition_to(x, fs, coffset, sig.fs, sig.fir_cutoff, ms_pad * per_ms, ntaps)
+
+
+def condition_to(x, fs, coffset, fs_out, cutoff, nout, ntaps=161):
+    """condition() with the output rate, the cut-off (Hz) and the output length given directly (what gacq_frontend_dev takes)."""
+    x = mix_fixed_point(x, -coffset / fs, 0)
+    fsr = fs_out / fs
+    h = scipy.signal.firwin(ntaps, cutoff / (fs / 2), window='hann')
     x = scipy.signal.filtfilt(h, [1], x)
-    t = (1 / fsr) * np.arange(ms_pad * per_ms)
+    t = (1 / fsr) * np.arange(nout)
     src = np.arange(len(x))
     return np.interp(t, src, np.real(x)) + 1j * np.interp(t, src, np.imag(x))

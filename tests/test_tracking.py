@@ -23,6 +23,17 @@ def test_oracle_matches_reference(case):
     assert p.real == pytest.approx(case["re"], rel=1e-12, abs=1e-10) and p.imag == pytest.approx(case["im"], rel=1e-12, abs=1e-10)
 
 
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_closed_form_oracle_matches_sequential_oracle(case):
+    """correlate_many (closed-form phases, the kernel's single-rounded fma form) == the pinned sequential correlate on every golden
+    case.  With the phases rounded twice (numpy's plain c + a*i) the gps.l1cd case would differ by one subcarrier sign (|dp| ~ 4)."""
+    from oracle import tracking_oracle
+    x = _x(case).astype(np.complex128)
+    a = tracking_oracle.correlate(case["code"], x, case["prn"], case["chips"], case["frac"], case["incr"])
+    b = tracking_oracle.correlate_many(case["code"], x, case["prn"], case["chips"], case["frac"], case["incr"])[0]
+    assert abs(a - b) <= 1e-12 * float(np.sum(np.abs(x)))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_gpu_matches_reference(engine, case):
