@@ -126,7 +126,7 @@ struct gacq_sig {
   float2* spectra_pfa = nullptr;   // same in the prime-factor engine's order (only when pfa_supported(N))
   float2* spectra_split = nullptr; // split engine with LDS inner transforms: R lane-pair rows per item (N = R*4096)
   float2* spectra_lds = nullptr;   // same in the LDS engine's lane-pair layout (only when lds_supported(N))
-  float2* spectra_lds16 = nullptr; // N = 16384 only: the order of the radix-16 form of the transform (GACQ_OPT_LDS_VARIANT = 16; spectra_lds holds the radix-32 form's, gacq_lds16k.hip)
+  float2* spectra_lds16 = nullptr; // N = 16384: the same in the radix-16 form's order (spectra_lds holds the radix-32 form's), built on first use
   double2* spectra64 = nullptr;    // complex128 code spectra of the verification engine (engine 5), built on first use
   double2* spectra64_split = nullptr;   // the same as R rows per item, [p][k1][k2] = C[k1 + R k2] (N = R x 4096: the split form of engine 5), built on first use
   std::vector<float> replica;      // host copy of the +-1 replicas [nprn][n] (source of spectra64)
@@ -165,30 +165,53 @@ int twiddle_cache(gacq_ctx* ctx, const std::string& key, int N, int count, const
 // arbitrary constant bytes cached per ctx under `key` (uploaded on first use)
 int table_cache(gacq_ctx* ctx, const std::string& key, const void* host, size_t bytes, const void** out);
 int fft_exec(gacq_ctx* ctx, int N, long batch, bool inverse, void* data, bool fp64 = false);
+// Which kernels serve a search: plan_search (gacq_engine.hip) decides it once per launch from the engine, the FFT length, the grid
+// and the options; launch_search and verify_search switch on it.
+enum class Form {
+  Fused4k, Fused16k,   // N = 4096, B = 1, one carrier / N = 16384, one carrier per item: forward + correlate in one kernel
+  Lds,                 // N = 4096 / 16384, the whole transform in one workgroup: forward kernel, correlate kernel (engine 2)
+  SplitLds,            // N = R x 4096: outer DFT-R, inner transforms on the LDS kernels (engine 4)
+  Pfa,                 // N = 61380 / 30690: the twiddle-free prime-factor form (gacq_pfa.hip)
+  SplitRocfft,         // Cooley-Tukey: outer DFT-R, rocFFT inner transforms (engine 3)
+  Rocfft,              // mix, rocFFT, conjugate multiply, rocFFT, magnitude / peak (engine 1)
+  // engine 5 (gacq_verify.hip): N = 4096 in one kernel (B = 1, one carrier) or a forward and a correlate kernel; N = 4 / 16 x 4096 split;
+  // N = 61380 / 30690 as 31 x M; the rocFFT double-precision pipeline
+  C128Fused4k, C128Lds4k, C128Split, C128R31, C128Rocfft,
+};
+struct SearchPlan {
+  Form form = Form::Rocfft;
+  // N = 16384, forms Lds / Fused16k: 32 = the radix-32 transform of gacq_lds16k.hip (default), 16 = the radix-16 one of gacq_ldsfft.hip
+  // (GACQ_OPT_LDS_VARIANT = 16: B1I 0-5 % slower, GLONASS within 2 % either way in the same process -- the in-run A/B of bench.py,
+  // roofline.ab.n16384_transform); 0 otherwise
+  int radix16k = 0;
+  bool c128() const { return form >= Form::C128Fused4k; }
+  bool fused() const { return form == Form::Fused4k || form == Form::Fused16k; }      // no forward-spectra buffer
+};
+
 // engine 5: the pipeline in complex128 on the device (gacq_verify.hip); ctx->freq / items / fset already uploaded
-int verify_search(gacq_sig* sig, XSrc d_x, size_t nsamp, int nepoch, int P, int F, int D, int B, gacq_peak* d_out, float* d_qrow);
+int verify_search(gacq_sig* sig, const SearchPlan& plan, XSrc d_x, size_t nsamp, int nepoch, int P, int F, int D, int B, gacq_peak* d_out,
+                  float* d_qrow);
 void stage_begin(gacq_ctx* ctx, int stage);
 void stage_end(gacq_ctx* ctx);
 
 // LDS-resident FFT engine (gacq_ldsfft.hip): supported lengths and the two launches.
 bool lds_supported(int N);
-int lds_code_spectra(gacq_ctx* ctx, const float2* replica_rows, float2* perm, int nprn, int N, bool radix16 = false);      // code spectra in the LDS engines' layout: the replicas through their own forward transform
+int lds_code_spectra(gacq_ctx* ctx, const float2* replica_rows, float2* perm, int nprn, int N);      // code spectra in the LDS engines' layout: the replicas through their own forward transform
 // X[row][k] = conj(FFT_N(x_window * nco))   rows = ((e*F + f)*D + d)*B + b
 int lds_forward(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, int n, int N, const double* d_freq,
                 int FD, int B, const float2* tab, float2* X);
 // rows[(e*P + p)*D + d] = reduce_k sum_b | IFFT_N(C_p * X[e,f(p),d,b]) | / N
 // N = 16384 with one carrier per item (F == P): forward + correlate in one kernel, no X buffer
-bool lds_fused_supported(const gacq_ctx* ctx, int N, int P, int F);
 int lds_fused_search(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, int n, int N, const float2* spectra, const int* d_items,
                      const int* d_fset, const double* d_freq, const float2* tab, int nitems, int D, int B, RowRec* rows, float tie_scale);
 // N = 4096, B == 1, one carrier: forward + correlate in one kernel, no X buffer
-bool lds_fused4k_supported(const gacq_ctx* ctx, int N, int B, int F, long units);
 int lds_fused4k_search(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, const float2* spectra, const int* d_items,
                        const double* d_freq, const float2* tab, int nitems, int D, RowRec* rows, float tie_scale);
 int lds_correlate(gacq_ctx* ctx, const float2* X, const float2* spectra, const int* d_items, const int* d_fset,
                   int nepoch, int nitems, int F, int D, int B, int N, RowRec* rows, float tie_scale, float* q_out = nullptr);
 
-// N = 16384 as 32 x 32 x 16 in one 512-thread workgroup (gacq_lds16k.hip): the launches behind the lds_* entry points above
+// N = 16384 as 32 x 32 x 16 in one 512-thread workgroup (gacq_lds16k.hip): the radix-32 counterparts of the lds_* entry points above,
+// which run the radix-16 form at that length
 int r32_code_spectra(gacq_ctx* ctx, const float2* replica_rows, float2* perm, int nprn);
 int r32_forward(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, int n, const double* d_freq, int FD, int B, const float2* tab,
                 float2* X);

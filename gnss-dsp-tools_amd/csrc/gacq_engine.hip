@@ -670,40 +670,32 @@ static int upload_replica_rows(gacq_sig* s, float2* dst) {
   return GACQ_OK;
 }
 
-// Code spectra in NATURAL order by rocFFT (c = fft.fft(c), acquire-gps-l1.py:24): what the rocFFT pipeline (engine 1) multiplies with and what
-// gacq_signal_spectrum hands out.  Built on first use: creating a rocFFT plan for a new length costs 0.5-2 s per process (runtime-compiled
-// kernels), and the default engines never need one -- their code spectra come out of their own forward transforms (build_signal).
-static int natural_spectra(gacq_sig* s) {
-  if (s->spectra) return GACQ_OK;
-  gacq_ctx* ctx = s->ctx;
-  const size_t bytes = sizeof(float2) * (size_t)s->nprn * s->N;
-  float2* buf = nullptr;
-  if (hipMalloc((void**)&buf, bytes) != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "hipMalloc of %zu bytes for code spectra failed", bytes);
-  int rc = upload_replica_rows(s, buf);
-  if (rc == GACQ_OK) rc = fft_exec(ctx, s->N, s->nprn, false, buf);
-  if (rc == GACQ_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_error(ctx, GACQ_ERR_HIP, "code spectrum FFT failed");
-  if (rc != GACQ_OK) { (void)hipFree(buf); return rc; }
-  s->spectra = buf;
-  return GACQ_OK;
-}
-
-// ... and in the [k1][k2] order of the Cooley-Tukey form of engine 3 with rocFFT inner transforms (GACQ_OPT_FUSED_INNER = 0): on first use
-static int ct_spectra(gacq_sig* s) {
-  if (s->spectra_r31) return GACQ_OK;
+// Code spectra in the order a form's forward transform produces: the replica rows go through transform(s, rows, out) -- in place
+// when in_place -- into *slot, unless *slot already exists.  The default forms' spectra are made with the signal by their own
+// transforms (build_signal: no rocFFT plan, whose creation costs 0.5-2 s per process and length); the others on first use
+// (code_spectra).
+static int ensure_spectra(gacq_sig* s, float2** slot, bool in_place, int (*transform)(gacq_sig*, float2*, float2*)) {
+  if (*slot) return GACQ_OK;
   gacq_ctx* ctx = s->ctx;
   const size_t bytes = sizeof(float2) * (size_t)s->nprn * s->N;
   float2 *buf = nullptr, *tmp = nullptr;
-  if (hipMalloc((void**)&buf, bytes) != hipSuccess || hipMalloc((void**)&tmp, bytes) != hipSuccess) {
+  if (hipMalloc((void**)&buf, bytes) != hipSuccess || (!in_place && hipMalloc((void**)&tmp, bytes) != hipSuccess)) {
     if (buf) (void)hipFree(buf);
-    return set_error(ctx, GACQ_ERR_HIP, "hipMalloc for radix-31 spectra failed");
+    return set_error(ctx, GACQ_ERR_HIP, "hipMalloc of %zu bytes for code spectra failed", bytes);
   }
-  int rc = upload_replica_rows(s, tmp);
-  if (rc == GACQ_OK) rc = split_forward(ctx, tmp, 0, s->nprn, s->N, s->N, nullptr, 1, 1, nullptr, buf, false);
-  if (rc == GACQ_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_error(ctx, GACQ_ERR_HIP, "split-engine code spectrum failed");
-  (void)hipFree(tmp);
+  float2* rows = in_place ? buf : tmp;
+  int rc = upload_replica_rows(s, rows);
+  if (rc == GACQ_OK) rc = transform(s, rows, buf);
+  if (rc == GACQ_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_error(ctx, GACQ_ERR_HIP, "code spectrum transform failed");
+  if (tmp) (void)hipFree(tmp);
   if (rc != GACQ_OK) { (void)hipFree(buf); return rc; }
-  s->spectra_r31 = buf;
+  *slot = buf;
   return GACQ_OK;
+}
+
+// NATURAL order by rocFFT (c = fft.fft(c), acquire-gps-l1.py:24): what the rocFFT pipeline multiplies with and gacq_signal_spectrum hands out
+static int natural_spectra(gacq_sig* s) {
+  return ensure_spectra(s, &s->spectra, true, [](gacq_sig* s, float2* rows, float2*) { return fft_exec(s->ctx, s->N, s->nprn, false, rows); });
 }
 
 static int build_signal(gacq_ctx* ctx, const gacq_sigdesc* desc, const std::vector<float>& replicas, int nprn, gacq_sig** out) {
@@ -714,41 +706,23 @@ static int build_signal(gacq_ctx* ctx, const gacq_sigdesc* desc, const std::vect
   s->nprn = nprn;
   s->N = desc->pad ? 2 * desc->n : desc->n;
   s->replica = replicas;
-  const size_t bytes = sizeof(float2) * (size_t)nprn * s->N;
+  const int N = s->N, R = split_radix(N);
   int rc = GACQ_OK;
-  // Every LDS-resident / split engine keeps the code spectra in the order ITS forward transform produces: the replicas go through
-  // that transform (no rocFFT plan is created here; natural_spectra() / ct_spectra() make the rocFFT-based forms when something asks).
-  const bool own = split_supported(s->N) || lds_supported(s->N);
-  float2* tmp = nullptr;
-  if (own) {
-    if (hipMalloc((void**)&tmp, bytes) != hipSuccess) rc = set_error(ctx, GACQ_ERR_HIP, "hipMalloc of %zu bytes for the replicas failed", bytes);
-    if (rc == GACQ_OK) rc = upload_replica_rows(s, tmp);
-  }
-  if (rc == GACQ_OK && split_supported(s->N)) {
-    if (s->N / split_radix(s->N) == 4096) {
-      // split engine with LDS inner transforms (N = R*4096): code spectra as R lane-pair rows per item
-      if (hipMalloc((void**)&s->spectra_split, bytes) != hipSuccess) rc = set_error(ctx, GACQ_ERR_HIP, "hipMalloc for split/LDS spectra failed");
-      if (rc == GACQ_OK) rc = split_forward(ctx, tmp, 0, nprn, s->N, s->N, nullptr, 1, 1, nullptr, s->spectra_split, false, false);
-      if (rc == GACQ_OK) rc = lds_inner_forward(ctx, s->spectra_split, (long)nprn * split_radix(s->N), false);
-    }
-    if (rc == GACQ_OK && pfa_supported(s->N)) {
-      // prime-factor engine: the spectrum order is whatever its forward kernels produce -- run the replicas through them
-      if (hipMalloc((void**)&s->spectra_pfa, bytes) != hipSuccess) rc = set_error(ctx, GACQ_ERR_HIP, "hipMalloc for prime-factor spectra failed");
-      if (rc == GACQ_OK) rc = pfa_forward(ctx, tmp, 0, nprn, s->N, s->N, nullptr, 1, 1, nullptr, s->spectra_pfa, false);
-    }
-  }
-  if (rc == GACQ_OK && lds_supported(s->N)) {
-    if (hipMalloc((void**)&s->spectra_lds, bytes) != hipSuccess) rc = set_error(ctx, GACQ_ERR_HIP, "hipMalloc for LDS-layout spectra failed");
-    else rc = lds_code_spectra(ctx, tmp, s->spectra_lds, nprn, s->N);
-    if (rc == GACQ_OK && s->N == 16384) {      // the radix-16 form of the N = 16384 transform has its own spectrum order (GACQ_OPT_LDS_VARIANT = 16)
-      if (hipMalloc((void**)&s->spectra_lds16, bytes) != hipSuccess) rc = set_error(ctx, GACQ_ERR_HIP, "hipMalloc for LDS-layout spectra failed");
-      else rc = lds_code_spectra(ctx, tmp, s->spectra_lds16, nprn, s->N, true);
-    }
-  }
-  if (rc == GACQ_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_error(ctx, GACQ_ERR_HIP, "code spectrum transform failed");
-  if (tmp) (void)hipFree(tmp);
-  if (rc == GACQ_OK && !own) rc = natural_spectra(s);      // lengths only the rocFFT pipeline serves
-  if (rc != GACQ_OK) { if (s->spectra) (void)hipFree(s->spectra); if (s->spectra_lds) (void)hipFree(s->spectra_lds); if (s->spectra_lds16) (void)hipFree(s->spectra_lds16); if (s->spectra_pfa) (void)hipFree(s->spectra_pfa); if (s->spectra_split) (void)hipFree(s->spectra_split); delete s; return rc; }
+  if (R && N / R == 4096)      // split engine with LDS inner transforms: R lane-pair rows per item
+    rc = ensure_spectra(s, &s->spectra_split, false, [](gacq_sig* s, float2* rows, float2* c) {
+      const int r = split_forward(s->ctx, rows, 0, s->nprn, s->N, s->N, nullptr, 1, 1, nullptr, c, false, false);
+      return r != GACQ_OK ? r : lds_inner_forward(s->ctx, c, (long)s->nprn * split_radix(s->N), false);
+    });
+  if (rc == GACQ_OK && pfa_supported(N))
+    rc = ensure_spectra(s, &s->spectra_pfa, false, [](gacq_sig* s, float2* rows, float2* c) {
+      return pfa_forward(s->ctx, rows, 0, s->nprn, s->N, s->N, nullptr, 1, 1, nullptr, c, false);
+    });
+  if (rc == GACQ_OK && lds_supported(N))      // N = 16384: the default radix-32 form's order
+    rc = ensure_spectra(s, &s->spectra_lds, false, [](gacq_sig* s, float2* rows, float2* c) {
+      return s->N == 16384 ? r32_code_spectra(s->ctx, rows, c, s->nprn) : lds_code_spectra(s->ctx, rows, c, s->nprn, s->N);
+    });
+  if (rc == GACQ_OK && !R && !lds_supported(N)) rc = natural_spectra(s);      // lengths only the rocFFT pipeline serves
+  if (rc != GACQ_OK) { gacq_signal_destroy(s); return rc; }
   *out = s;
   return GACQ_OK;
 }
@@ -848,21 +822,74 @@ Grid make_grid(const gacq_sigdesc& d, int nitems, const double* dopplers, int nd
   return g;
 }
 
-// Which kernels of the LDS-resident engine serve a search -- decided in ONE place for the launch sequence (launch_search) and for
-// the Doppler-slicing decision of gacq_search_batch_dev, which must know whether a forward-spectra buffer exists at all.
-struct LdsPath {
-  bool use_lds = false;      // whole transform in one workgroup (engine 2, or auto where the length is supported)
-  bool fused16k = false;     // N = 16384, one carrier per item: forward + correlate in one kernel
-  bool fused4k = false;      // N = 4096, B = 1, one carrier: forward + correlate in one kernel
-  bool no_forward_buffer() const { return fused16k || fused4k; }
-};
-LdsPath lds_path(const gacq_ctx* ctx, int N, int nepoch, int P, int F, int D, int B, bool row_dump) {
-  LdsPath p;
-  p.use_lds = (ctx->engine == 2) || (ctx->engine == 0 && lds_supported(N) && !row_dump);
-  if (!p.use_lds || !lds_supported(N) || row_dump) return p;      // a row dump (engine 2) goes through the two-kernel path
-  p.fused16k = lds_fused_supported(ctx, N, P, F);
-  p.fused4k = !p.fused16k && lds_fused4k_supported(ctx, N, B, F, (long)nepoch * D);
-  return p;
+int lds16k_radix(const gacq_ctx* ctx) { return ctx->opt[GACQ_OPT_LDS_VARIANT] == 16 ? 16 : 32; }      // the form of the N = 16384 LDS transform
+
+// The one decision of which kernels serve a search (P items over F carriers, D Doppler bins, B blocks, nepoch epochs).  A row dump
+// (gacq_debug_row) runs the engine that was asked for, and the rocFFT pipeline for auto; it never takes a fused form.
+int plan_search(gacq_ctx* ctx, int N, int nepoch, int P, int F, int D, int B, bool row_dump, SearchPlan* plan) {
+  const int e = (row_dump && ctx->engine == 0) ? 1 : ctx->engine;
+  const int R = split_radix(N);
+  const bool split_lds = R != 0 && N / R == 4096;
+  *plan = SearchPlan{};
+  if (e == 5) {
+    // the hand-written complex128 kernels where they exist; GACQ_OPT_FUSED_C128 = 0 keeps the rocFFT pipeline (the cross-check)
+    const bool c = ctx->opt[GACQ_OPT_FUSED_C128] != 0;
+    if (c && N == 4096 && !row_dump) plan->form = (B == 1 && F == 1) ? Form::C128Fused4k : Form::C128Lds4k;
+    else if (c && (N == 16384 || N == 65536)) plan->form = Form::C128Split;
+    else if (c && (N == 61380 || N == 30690)) plan->form = Form::C128R31;
+    else plan->form = Form::C128Rocfft;
+    return GACQ_OK;
+  }
+  if (e == 2 && !lds_supported(N)) return set_error(ctx, GACQ_ERR_UNSUPPORTED, "engine 2 (LDS FFT) does not support N=%d", N);
+  if (e == 4 && !split_lds)
+    return set_error(ctx, GACQ_ERR_UNSUPPORTED, "engine 4 (split with LDS inner transforms) does not support N=%d", N);
+  if (e == 3 && !split_supported(N))
+    return set_error(ctx, GACQ_ERR_UNSUPPORTED, "engine 3 (split with rocFFT inner transforms) does not support N=%d", N);
+  if (e == 2 || (e == 0 && lds_supported(N))) {
+    // N = 4096 fused: worth it for batches only -- with few (epoch, Doppler) units every workgroup's own forward transform sits on
+    // the critical path (single epoch: 32 us fused against 19 us for the two kernels), with many it replaces a launch, 84 MB of X
+    // traffic and a tail
+    const long fuse4k = ctx->opt[GACQ_OPT_FUSED_4K];
+    if (!row_dump && N == 16384 && F == P && ctx->opt[GACQ_OPT_FUSED_16K]) plan->form = Form::Fused16k;
+    else if (!row_dump && N == 4096 && B == 1 && F == 1 && (fuse4k >= 2 || (fuse4k == 1 && (long)nepoch * D >= 1024))) plan->form = Form::Fused4k;
+    else plan->form = Form::Lds;
+    if (N == 16384) plan->radix16k = lds16k_radix(ctx);
+  } else if (e == 4 || (e == 0 && split_lds)) {
+    plan->form = Form::SplitLds;
+  } else if (e == 3 || (e == 0 && split_supported(N))) {
+    // N = 31 x 1980 / 31 x 990: the twiddle-free prime-factor form unless the caller asks for the Cooley-Tukey form with rocFFT inner
+    // transforms (GACQ_OPT_FUSED_INNER = 0: other arithmetic, the cross-check)
+    plan->form = (pfa_supported(N) && ctx->opt[GACQ_OPT_FUSED_INNER] != 0) ? Form::Pfa : Form::SplitRocfft;
+  } else {
+    plan->form = Form::Rocfft;
+  }
+  return GACQ_OK;
+}
+
+// The code spectra a form multiplies with; the Cooley-Tukey form of engine 3 (GACQ_OPT_FUSED_INNER = 0), the rocFFT pipeline and the
+// radix-16 form of the N = 16384 transform (GACQ_OPT_LDS_VARIANT = 16) have theirs made on first use
+int code_spectra(gacq_sig* s, const SearchPlan& plan, const float2** out) {
+  int rc = GACQ_OK;
+  switch (plan.form) {
+    case Form::Fused4k: case Form::Fused16k: case Form::Lds:
+      if (plan.radix16k == 16)
+        rc = ensure_spectra(s, &s->spectra_lds16, false, [](gacq_sig* s, float2* rows, float2* c) {
+          return lds_code_spectra(s->ctx, rows, c, s->nprn, s->N);
+        });
+      *out = plan.radix16k == 16 ? s->spectra_lds16 : s->spectra_lds;
+      break;
+    case Form::SplitLds: *out = s->spectra_split; break;
+    case Form::Pfa: *out = s->spectra_pfa; break;
+    case Form::SplitRocfft:      // [k1][k2] order
+      rc = ensure_spectra(s, &s->spectra_r31, false, [](gacq_sig* s, float2* rows, float2* c) {
+        return split_forward(s->ctx, rows, 0, s->nprn, s->N, s->N, nullptr, 1, 1, nullptr, c, false);
+      });
+      *out = s->spectra_r31;
+      break;
+    case Form::Rocfft: rc = natural_spectra(s); *out = s->spectra; break;
+    default: *out = nullptr;      // engine 5: complex128 spectra of its own (gacq_verify.hip)
+  }
+  return rc;
 }
 
 // NCO frequencies [F][D], forward-set index and item index per position -> ctx->freq / fset / items on the device (skipped when the
@@ -924,6 +951,9 @@ int upload_grid(gacq_sig* sig, int nepoch, const int* items, int nitems, const d
   return GACQ_OK;
 }
 
+// one stage of a search under its stage timer (gacq_get_stage_time)
+template <class Run> int timed(gacq_ctx* ctx, int stage, Run run) { stage_begin(ctx, stage); const int rc = run(); stage_end(ctx); return rc; }
+
 // xs: the samples as the caller gave them (complex64 or complex128); d_x: their complex64 form for the fp32 engines (== xs.p for
 // complex64 input, a rounded copy for complex128 input, unused by engine 5)
 int launch_search(gacq_sig* sig, XSrc xs, const float2* d_x, size_t nsamp, int nepoch, const int* items, int nitems,
@@ -936,25 +966,11 @@ int launch_search(gacq_sig* sig, XSrc xs, const float2* d_x, size_t nsamp, int n
   int rc = upload_grid(sig, nepoch, items, nitems, dopplers, nd, bias, &F);
   if (rc != GACQ_OK) return rc;
 
-  if (ctx->engine == 5) return verify_search(sig, xs, nsamp, nepoch, P, F, D, B, d_out, d_qrow);      // complex128 engine: reads the samples as given
-
-  const LdsPath path = lds_path(ctx, N, nepoch, P, F, D, B, d_qrow != nullptr);
-  const bool use_lds = path.use_lds;
-  if (ctx->engine == 2 && !lds_supported(N))
-    return set_error(ctx, GACQ_ERR_UNSUPPORTED, "engine 2 (LDS FFT) does not support N=%d", N);
-  const int R = split_radix(N);
-  const bool split_lds_ok = R != 0 && N / R == 4096;
-  const bool use_split_lds = (ctx->engine == 4) || (ctx->engine == 0 && split_lds_ok);
-  if (ctx->engine == 4 && !split_lds_ok)
-    return set_error(ctx, GACQ_ERR_UNSUPPORTED, "engine 4 (split with LDS inner transforms) does not support N=%d", N);
-  const bool use_split = use_split_lds || (ctx->engine == 3) || (ctx->engine == 0 && split_supported(N));
-  // N = 31 * 1980 / 31 * 990: the twiddle-free prime-factor form (gacq_pfa.hip) unless the caller asks for the Cooley-Tukey forms
-  // form with rocFFT inner transforms (GACQ_OPT_FUSED_INNER 0: other arithmetic, the cross-check)
-  const bool use_pfa = use_split && !use_split_lds && pfa_supported(N) && ctx->opt[GACQ_OPT_FUSED_INNER] != 0;
-  if (ctx->engine == 3 && !split_supported(N))
-    return set_error(ctx, GACQ_ERR_UNSUPPORTED, "engine 3 (split with rocFFT inner transforms) does not support N=%d", N);
-  // the forms that multiply with rocFFT-made code spectra build them now, on first use (natural order / Cooley-Tukey [k1][k2] order)
-  if (!use_lds && !use_split_lds && !use_pfa && (rc = use_split ? ct_spectra(sig) : natural_spectra(sig)) != GACQ_OK) return rc;
+  SearchPlan plan;
+  if ((rc = plan_search(ctx, N, nepoch, P, F, D, B, d_qrow != nullptr, &plan)) != GACQ_OK) return rc;
+  if (plan.c128()) return verify_search(sig, plan, xs, nsamp, nepoch, P, F, D, B, d_out, d_qrow);      // complex128 engine: reads the samples as given
+  const float2* C;
+  if ((rc = code_spectra(sig, plan, &C)) != GACQ_OK) return rc;
 
   // tie-safe locations: the reducers tag rows whose runner-up lag is within eps of the maximum, best_doppler_kernel lists the
   // (epoch, item) pairs it cannot decide and gacq_tiesafe.hip re-evaluates their candidate rows in complex128
@@ -967,71 +983,63 @@ int launch_search(gacq_sig* sig, XSrc xs, const float2* d_x, size_t nsamp, int n
     if ((rc = tie_lists(ctx, (long)nepoch * P, N, B, &tl, &guesses)) != GACQ_OK) return rc;
   }
 
-  // epochs per pass so that the forward-spectra buffer respects the workspace limit
-  const bool fused16k = path.fused16k;      // one carrier per item: no forward-spectra buffer at all
+  // epochs per pass so that the forward-spectra buffer respects the workspace limit; the fused forms buffer nothing but the 16-byte
+  // row records
   const size_t x_epoch_bytes = sizeof(float2) * (size_t)F * D * B * N;
-  int Ec = (int)std::max<size_t>(1, std::min<size_t>((size_t)nepoch, ws_budget(ctx) / std::max<size_t>(1, x_epoch_bytes)));
-  const bool fused4k = path.fused4k;
-  if (fused16k || fused4k) Ec = nepoch;            // nothing but the 16-byte row records is buffered
-  if (!fused16k && !fused4k && (rc = ensure(ctx, ctx->X, x_epoch_bytes * Ec)) != GACQ_OK) return rc;
+  const int Ec = plan.fused() ? nepoch : (int)std::max<size_t>(1, std::min<size_t>((size_t)nepoch, ws_budget(ctx) / std::max<size_t>(1, x_epoch_bytes)));
+  if (!plan.fused() && (rc = ensure(ctx, ctx->X, x_epoch_bytes * Ec)) != GACQ_OK) return rc;
   if ((rc = ensure(ctx, ctx->rows, sizeof(RowRec) * (size_t)Ec * P * D)) != GACQ_OK) return rc;
 
+  const int R = split_radix(N);
   const int chunksN = (N + kBlock * 8 - 1) / (kBlock * 8);
-  const float2* lds_spectra = (N == 16384 && ctx->opt[GACQ_OPT_LDS_VARIANT] == 16) ? sig->spectra_lds16 : sig->spectra_lds;
+  const bool r32 = plan.radix16k == 32;
+  const int* d_items = (const int*)ctx->items.p;
+  const int* d_fset = (const int*)ctx->fset.p;
+  const double* d_freq = (const double*)ctx->freq.p;
+  const float2* tab = (const float2*)ctx->tab.p;
   for (int e0 = 0; e0 < nepoch; e0 += Ec) {
     const int ne = std::min(Ec, nepoch - e0);
     const float2* xe = d_x + (size_t)e0 * nsamp;
     float2* X = (float2*)ctx->X.p;
     RowRec* rows = (RowRec*)ctx->rows.p;
     const long rows_x = (long)ne * F * D * B;
-    if (fused16k) {
-      stage_begin(ctx, 6);
-      rc = lds_fused_search(ctx, xe, nsamp, ne, n, N, lds_spectra, (const int*)ctx->items.p, (const int*)ctx->fset.p,
-                            (const double*)ctx->freq.p, (const float2*)ctx->tab.p, P, D, B, rows, tscale);
-      stage_end(ctx);
-      if (rc != GACQ_OK) return rc;
-    } else if (fused4k) {
-      stage_begin(ctx, 6);
-      rc = lds_fused4k_search(ctx, xe, nsamp, ne, sig->spectra_lds, (const int*)ctx->items.p, (const double*)ctx->freq.p, (const float2*)ctx->tab.p, P, D, rows,
-                              tscale);
-      stage_end(ctx);
-      if (rc != GACQ_OK) return rc;
-    } else if (use_lds) {
-      stage_begin(ctx, 0);
-      rc = lds_forward(ctx, xe, nsamp, ne, n, N, (const double*)ctx->freq.p, F * D, B, (const float2*)ctx->tab.p, X);
-      stage_end(ctx);
-      if (rc != GACQ_OK) return rc;
-      stage_begin(ctx, 6);
-      rc = lds_correlate(ctx, X, lds_spectra, (const int*)ctx->items.p, (const int*)ctx->fset.p, ne, P, F, D, B, N, rows, tscale, d_qrow);
-      stage_end(ctx);
-      if (rc != GACQ_OK) return rc;
-    } else {
-      if (use_pfa) {
+    switch (plan.form) {
+      case Form::Fused16k:
+        rc = timed(ctx, 6, [&] {
+          return r32 ? r32_fused_search(ctx, xe, nsamp, ne, n, C, d_items, d_fset, d_freq, tab, P, D, B, rows, tscale)
+                     : lds_fused_search(ctx, xe, nsamp, ne, n, N, C, d_items, d_fset, d_freq, tab, P, D, B, rows, tscale);
+        });
+        break;
+      case Form::Fused4k: rc = timed(ctx, 6, [&] { return lds_fused4k_search(ctx, xe, nsamp, ne, C, d_items, d_freq, tab, P, D, rows, tscale); }); break;
+      case Form::Lds:
+        rc = timed(ctx, 0, [&] {
+          return r32 ? r32_forward(ctx, xe, nsamp, ne, n, d_freq, F * D, B, tab, X) : lds_forward(ctx, xe, nsamp, ne, n, N, d_freq, F * D, B, tab, X);
+        });
+        if (rc == GACQ_OK) rc = timed(ctx, 6, [&] {
+          return r32 ? r32_correlate(ctx, X, C, d_items, d_fset, ne, P, F, D, B, rows, tscale, d_qrow)
+                     : lds_correlate(ctx, X, C, d_items, d_fset, ne, P, F, D, B, N, rows, tscale, d_qrow);
+        });
+        break;
+      case Form::Pfa: rc = timed(ctx, 0, [&] { return pfa_forward(ctx, xe, nsamp, rows_x, n, N, d_freq, F * D, B, tab, X, true); }); break;
+      case Form::SplitLds: case Form::SplitRocfft:
+        rc = timed(ctx, 0, [&] {
+          const int r = split_forward(ctx, xe, nsamp, rows_x, n, N, d_freq, F * D, B, tab, X, true, plan.form == Form::SplitRocfft);
+          return (r == GACQ_OK && plan.form == Form::SplitLds) ? lds_inner_forward(ctx, X, rows_x * R, true) : r;
+        });
+        break;
+      default:      // Form::Rocfft
         stage_begin(ctx, 0);
-        rc = pfa_forward(ctx, xe, nsamp, rows_x, n, N, (const double*)ctx->freq.p, F * D, B, (const float2*)ctx->tab.p, X, true);
-        stage_end(ctx);
-        if (rc != GACQ_OK) return rc;
-      } else if (use_split) {
-        stage_begin(ctx, 0);
-        rc = split_forward(ctx, xe, nsamp, rows_x, n, N, (const double*)ctx->freq.p, F * D, B, (const float2*)ctx->tab.p, X, true,
-                         !use_split_lds);
-        if (rc == GACQ_OK && use_split_lds) rc = lds_inner_forward(ctx, X, rows_x * R, true);
-        stage_end(ctx);
-        if (rc != GACQ_OK) return rc;
-      } else {
-        stage_begin(ctx, 0);
-        hipLaunchKernelGGL(mix_nco_kernel<false>, dim3((unsigned)(rows_x * chunksN)), dim3(kBlock), 0, st, xe, nsamp, X,
-                           (const double*)ctx->freq.p, (const float2*)ctx->tab.p, n, N, F * D, B, chunksN);
+        hipLaunchKernelGGL(mix_nco_kernel<false>, dim3((unsigned)(rows_x * chunksN)), dim3(kBlock), 0, st, xe, nsamp, X, d_freq, tab, n, N,
+                           F * D, B, chunksN);
         stage_end(ctx);
         GACQ_HIP(ctx, hipGetLastError());
-        stage_begin(ctx, 1);
-        rc = fft_exec(ctx, N, rows_x, false, X);
-        stage_end(ctx);
-        if (rc != GACQ_OK) return rc;
-      }
+        rc = timed(ctx, 1, [&] { return fft_exec(ctx, N, rows_x, false, X); });
+    }
+    if (rc != GACQ_OK) return rc;
+    if (plan.form != Form::Lds && !plan.fused()) {
       // correlation workspace: chunks of whole (e,p,d) groups, B rows each
       const long groups = (long)ne * P * D;
-      const int zpitch = use_pfa ? pfa_row_pitch(N) : 0;       // prime-factor engine: Z' rows are whole reader workgroups of 128-byte lines
+      const int zpitch = plan.form == Form::Pfa ? pfa_row_pitch(N) : 0;       // prime-factor engine: Z' rows are whole reader workgroups of 128-byte lines
       const size_t group_bytes = sizeof(float2) * (size_t)B * (zpitch ? (size_t)zpitch * R : (size_t)N);
       // One pass of Z' is at most 4 GiB, or eight items' worth where that is more (the writers share their forward-spectrum tiles
       // over up to eight items of a pass: a B = 80 search of engine 3 holds 1.4 items in 4 GiB and runs 22 % slower for it).  Beyond
@@ -1045,60 +1053,39 @@ int launch_search(gacq_sig* sig, XSrc xs, const float2* d_x, size_t nsamp, int n
       float2* Y = (float2*)ctx->Y.p;
       for (long g0 = 0; g0 < groups; g0 += gc) {
         const long ng = std::min(gc, groups - g0);
-        if (use_split_lds) {
-          stage_begin(ctx, 6);
-          rc = lds_inner_correlate(ctx, X, sig->spectra_split, (const int*)ctx->items.p, (const int*)ctx->fset.p, g0, ng, P, F, D, B, R,
-                                   N, Y);                                       // K2 + inner inverse FFT + twiddle, fused
-          stage_end(ctx);
-          if (rc != GACQ_OK) return rc;
-          stage_begin(ctx, 4);
-          rc = split_inverse_reduce(ctx, Y, rows, g0, ng, B, N, d_qrow, tscale, false);   // outer inverse DFT + |.| + reduce
-          stage_end(ctx);
-          if (rc != GACQ_OK) return rc;
-          continue;
+        switch (plan.form) {
+          case Form::SplitLds:      // K2 + inner inverse FFT + twiddle, fused; then outer inverse DFT + |.| + reduce
+            rc = timed(ctx, 6, [&] { return lds_inner_correlate(ctx, X, C, d_items, d_fset, g0, ng, P, F, D, B, R, N, Y); });
+            if (rc == GACQ_OK) rc = timed(ctx, 4, [&] { return split_inverse_reduce(ctx, Y, rows, g0, ng, B, N, d_qrow, tscale, false); });
+            break;
+          case Form::Pfa:      // K2 + inner inverse transforms, in place in LDS; then inverse DFT-31 + |.| + reduce
+            rc = timed(ctx, 6, [&] { return pfa_inner_correlate(ctx, X, C, d_items, d_fset, g0, ng, P, F, D, B, N, Y); });
+            if (rc == GACQ_OK)
+              rc = timed(ctx, 4, [&] { return pfa_inverse_reduce(ctx, Y, rows, g0, ng, B, N, d_qrow, tscale, ds.metric_mode != 0); });
+            break;
+          default:      // Form::SplitRocfft, Form::Rocfft
+            stage_begin(ctx, 2);
+            hipLaunchKernelGGL(conj_mul_kernel, dim3((unsigned)(ng * B * chunksN)), dim3(kBlock), 0, st, X, C, Y, d_items, d_fset, g0, P, F, D, B,
+                               N, chunksN);
+            stage_end(ctx);
+            GACQ_HIP(ctx, hipGetLastError());
+            // Cooley-Tukey: inner inverse FFTs + outer DFT-31 + |.| + reduce; pipeline: the inverse FFT, then magnitudes and peaks
+            rc = timed(ctx, 3, [&] {
+              return plan.form == Form::SplitRocfft ? split_inverse_reduce(ctx, Y, rows, g0, ng, B, N, d_qrow, tscale) : fft_exec(ctx, N, ng * B, true, Y);
+            });
+            if (rc != GACQ_OK || plan.form == Form::SplitRocfft) break;
+            stage_begin(ctx, 4);
+            hipLaunchKernelGGL(mag_peak_kernel, dim3((unsigned)ng), dim3(kBlock), 0, st, Y, rows, g0, B, N, 1.0f / (float)N, d_qrow, tscale);
+            stage_end(ctx);
+            GACQ_HIP(ctx, hipGetLastError());
         }
-        if (use_pfa) {
-          stage_begin(ctx, 6);
-          rc = pfa_inner_correlate(ctx, X, sig->spectra_pfa, (const int*)ctx->items.p, (const int*)ctx->fset.p, g0, ng, P, F, D, B, N, Y);   // K2 + inner inverse transforms, in place in LDS
-          stage_end(ctx);
-          if (rc != GACQ_OK) return rc;
-          stage_begin(ctx, 4);
-          rc = pfa_inverse_reduce(ctx, Y, rows, g0, ng, B, N, d_qrow, tscale, ds.metric_mode != 0);                 // inverse DFT-31 + |.| + reduce
-          stage_end(ctx);
-          if (rc != GACQ_OK) return rc;
-          continue;
-        }
-        stage_begin(ctx, 2);
-        hipLaunchKernelGGL(conj_mul_kernel, dim3((unsigned)(ng * B * chunksN)), dim3(kBlock), 0, st, X,
-                           use_split ? sig->spectra_r31 : sig->spectra, Y,
-                           (const int*)ctx->items.p, (const int*)ctx->fset.p, g0, P, F, D, B, N, chunksN);
-        stage_end(ctx);
-        GACQ_HIP(ctx, hipGetLastError());
-        if (use_split) {
-          stage_begin(ctx, 3);
-          rc = split_inverse_reduce(ctx, Y, rows, g0, ng, B, N, d_qrow, tscale);      // inner inverse FFTs + outer DFT-31 + |.| + reduce
-          stage_end(ctx);
-          if (rc != GACQ_OK) return rc;
-        } else {
-          stage_begin(ctx, 3);
-          rc = fft_exec(ctx, N, ng * B, true, Y);
-          stage_end(ctx);
-          if (rc != GACQ_OK) return rc;
-          stage_begin(ctx, 4);
-          hipLaunchKernelGGL(mag_peak_kernel, dim3((unsigned)ng), dim3(kBlock), 0, st, Y, rows, g0, B, N, 1.0f / (float)N, d_qrow, tscale);
-          stage_end(ctx);
-          GACQ_HIP(ctx, hipGetLastError());
-        }
+        if (rc != GACQ_OK) return rc;
       }
     }
     const long nep = (long)ne * P;
     stage_begin(ctx, 5);
-    if (tie)
-      hipLaunchKernelGGL(best_doppler_kernel<true>, dim3((unsigned)((nep + 3) / 4)), dim3(256), 0, st, rows, d_out + (size_t)e0 * P, nep, D, N,
-                         ds.metric_mode, tl, guesses, tscale);
-    else
-      hipLaunchKernelGGL(best_doppler_kernel<false>, dim3((unsigned)((nep + 3) / 4)), dim3(256), 0, st, rows, d_out + (size_t)e0 * P, nep, D, N,
-                         ds.metric_mode, tl, guesses, tscale);
+    hipLaunchKernelGGL(tie ? best_doppler_kernel<true> : best_doppler_kernel<false>, dim3((unsigned)((nep + 3) / 4)), dim3(256), 0, st, rows,
+                       d_out + (size_t)e0 * P, nep, D, N, ds.metric_mode, tl, guesses, tscale);
     stage_end(ctx);
     GACQ_HIP(ctx, hipGetLastError());
     if (tie && (rc = tie_resolve(sig, tl, guesses, xs.offset((size_t)e0 * nsamp), nsamp, P, D, B, d_out + (size_t)e0 * P)) != GACQ_OK) return rc;
@@ -1257,9 +1244,10 @@ static int search_batch_dev_once(gacq_sig* sig, XSrc xs, size_t nsamp, int nepoc
     for (int p = 0; p < nitems; p++) if (std::find(seen.begin(), seen.end(), item_bias_hz[p]) == seen.end()) seen.push_back(item_bias_hz[p]);
     F = (int)seen.size();
   }
-  const size_t bin_bytes = (ctx->engine == 5 ? sizeof(double2) : sizeof(float2)) * (size_t)F * blocks * sig->N;
-  const bool no_x = lds_path(ctx, sig->N, nepoch, nitems, F, nd, blocks, false).no_forward_buffer();
-  if (!no_x && nd > 1 && bin_bytes * nd > ws_budget(ctx)) {
+  SearchPlan plan;
+  if ((rc = plan_search(ctx, sig->N, nepoch, nitems, F, nd, blocks, false, &plan)) != GACQ_OK) return rc;
+  const size_t bin_bytes = (plan.c128() ? sizeof(double2) : sizeof(float2)) * (size_t)F * blocks * sig->N;
+  if (!plan.fused() && nd > 1 && bin_bytes * nd > ws_budget(ctx)) {
     const int Dc = (int)std::max<size_t>(1, ws_budget(ctx) / bin_bytes);
     const int nch = (nd + Dc - 1) / Dc;
     const long n = (long)nepoch * nitems;
@@ -1513,9 +1501,11 @@ int gacq_debug_nco_indices(gacq_sig* sig, int kernel, double doppler, double bia
       GACQ_HIP(ctx, hipGetLastError());
       break;
     }
-    case 2: rc = lds_debug_nco(ctx, N, n, (const double*)ctx->freq.p, false, d_idx); break;
+    case 2: case 4:      // N = 16384: the form of the transform a search would run (plan_search)
+      rc = (N == 16384 && lds16k_radix(ctx) == 32) ? r32_debug_nco(ctx, n, (const double*)ctx->freq.p, kernel == 4, d_idx)
+                                                   : lds_debug_nco(ctx, N, n, (const double*)ctx->freq.p, kernel == 4, d_idx);
+      break;
     case 3: rc = split_debug_nco(ctx, N, n, (const double*)ctx->freq.p, d_idx); break;
-    case 4: rc = lds_debug_nco(ctx, N, n, (const double*)ctx->freq.p, true, d_idx); break;
     case 5: rc = pfa_debug_nco(ctx, N, n, (const double*)ctx->freq.p, d_idx); break;
     default: rc = set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_debug_nco_indices: kernel must be 1..5");
   }
@@ -1542,13 +1532,9 @@ int gacq_debug_row(gacq_sig* sig, const float* x_iq, size_t nsamp, int item, dou
     (void)hipFree(d_q);
     return set_error(ctx, GACQ_ERR_HIP, "gacq_debug_row: H2D failed");
   }
-  const int saved = ctx->engine;
-  // row dump: the engine that was asked for -- rocFFT pipeline (also what auto means here), LDS kernels (two-kernel path), split
-  // engines, fp64 pipeline
-  ctx->engine = (saved >= 2 && saved <= 5) ? saved : 1;
+  // row dump: the engine that was asked for, the rocFFT pipeline for auto (plan_search)
   rc = launch_search(sig, XSrc{ctx->xstage.p, 0}, (const float2*)ctx->xstage.p, need, 1, &item, 1, &doppler, 1, bias_hz != 0.0 ? &bias_hz : nullptr, blocks,
                      (gacq_peak*)ctx->out_peaks.p, d_q);
-  ctx->engine = saved;
   if (rc == GACQ_OK && hipMemcpyAsync(q_out, d_q, sizeof(float) * sig->N, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
     rc = set_error(ctx, GACQ_ERR_HIP, "gacq_debug_row: D2H failed");
   if (rc == GACQ_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_error(ctx, GACQ_ERR_HIP, "gacq_debug_row: sync failed");

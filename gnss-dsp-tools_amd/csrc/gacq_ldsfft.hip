@@ -994,11 +994,8 @@ int twiddle_table(gacq_ctx* ctx, const float2** out) { return twiddle_cache(ctx,
 
 namespace gacq {
 
+// N = 16384 here is the radix-16 form of the transform; plan_search (gacq_engine.hip) picks it or the radix-32 form (gacq_lds16k.hip)
 bool lds_supported(int N) { return N == kLdsN || N == kBig; }
-
-// N = 16384: the radix-32 form of gacq_lds16k.hip unless GACQ_OPT_LDS_VARIANT = 16 selects the radix-16 form of this file (B1I 0-5 %
-// slower, GLONASS within 2 % either way in the same process: the in-run A/B of bench.py, roofline.ab.n16384_transform)
-static bool radix16_16k(const gacq_ctx* ctx) { return ctx->opt[GACQ_OPT_LDS_VARIANT] == 16; }
 
 #ifdef GACQ_PHASE_TIMING16
 extern "C" int gacq_debug_phase16(unsigned long long* out128, int reset) {
@@ -1012,9 +1009,8 @@ extern "C" int gacq_debug_phase16(unsigned long long* out128, int reset) {
 #endif
 
 // code spectra straight from the (complex, zero-extended) replica rows with the engine's own forward transform: no rocFFT plan
-int lds_code_spectra(gacq_ctx* ctx, const float2* replica_rows, float2* perm, int nprn, int N, bool radix16) {
+int lds_code_spectra(gacq_ctx* ctx, const float2* replica_rows, float2* perm, int nprn, int N) {
   if (!lds_supported(N)) return set_error(ctx, GACQ_ERR_UNSUPPORTED, "LDS FFT engine: N=%d not supported", N);
-  if (N == kBig && !radix16) return r32_code_spectra(ctx, replica_rows, perm, nprn);
   if (N == kBig) {
     const float2* twn;
     int rcb = twiddle_cache(ctx, "W16384_lo", kBig, 1024, &twn);
@@ -1037,7 +1033,6 @@ int lds_code_spectra(gacq_ctx* ctx, const float2* replica_rows, float2* perm, in
 int lds_forward(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, int n, int N, const double* d_freq, int FD,
                 int B, const float2* tab, float2* X) {
   if (!lds_supported(N)) return set_error(ctx, GACQ_ERR_UNSUPPORTED, "LDS FFT engine: N=%d not supported", N);
-  if (N == kBig && !radix16_16k(ctx)) return r32_forward(ctx, x, nsamp, nepoch, n, d_freq, FD, B, tab, X);
   if (N == kBig) {
     const float2* twn;
     int rcb = twiddle_cache(ctx, "W16384_lo", kBig, 1024, &twn);
@@ -1057,12 +1052,9 @@ int lds_forward(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, int n,
   return GACQ_OK;
 }
 
-bool lds_fused_supported(const gacq_ctx* ctx, int N, int P, int F) { return N == kBig && F == P && ctx->opt[GACQ_OPT_FUSED_16K]; }
-
 int lds_fused_search(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, int n, int N, const float2* spectra, const int* d_items,
                      const int* d_fset, const double* d_freq, const float2* tab, int nitems, int D, int B, RowRec* rows, float tie_scale) {
   if (N != kBig) return set_error(ctx, GACQ_ERR_UNSUPPORTED, "fused LDS search: N=%d not supported", N);
-  if (!radix16_16k(ctx)) return r32_fused_search(ctx, x, nsamp, nepoch, n, spectra, d_items, d_fset, d_freq, tab, nitems, D, B, rows, tie_scale);
   const float2* twn;
   int rc = twiddle_cache(ctx, "W16384_lo", kBig, 1024, &twn);
   if (rc != GACQ_OK) return rc;
@@ -1071,12 +1063,6 @@ int lds_fused_search(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, i
                      nsamp, spectra, d_items, d_fset, d_freq, tab, twn, rows, n, nitems, D, B, tie_scale);
   GACQ_HIP(ctx, hipGetLastError());
   return GACQ_OK;
-}
-
-// Worth it for batches only: with few (epoch, Doppler) units every workgroup's own forward transform sits on the critical path
-// (single epoch: 32 us fused against 19 us for the two kernels), with many it replaces a launch, 84 MB of X traffic and a tail.
-bool lds_fused4k_supported(const gacq_ctx* ctx, int N, int B, int F, long units) {
-  return N == kLdsN && B == 1 && F == 1 && (ctx->opt[GACQ_OPT_FUSED_4K] >= 2 || (ctx->opt[GACQ_OPT_FUSED_4K] == 1 && units >= 1024));
 }
 
 int lds_fused4k_search(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, const float2* spectra, const int* d_items,
@@ -1102,7 +1088,6 @@ int lds_fused4k_search(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch,
 
 int lds_debug_nco(gacq_ctx* ctx, int N, int n, const double* d_freq, bool fused, int* d_idx) {
   if (!lds_supported(N) || (fused && N != kBig)) return set_error(ctx, GACQ_ERR_UNSUPPORTED, "NCO index dump: no %sLDS forward kernel for N=%d", fused ? "fused " : "", N);
-  if (N == kBig && !radix16_16k(ctx)) return r32_debug_nco(ctx, n, d_freq, fused, d_idx);
   if (N == kBig && fused) {
     int rc = ensure(ctx, ctx->fset, sizeof(int));
     if (rc != GACQ_OK) return rc;
@@ -1128,7 +1113,6 @@ int lds_correlate(gacq_ctx* ctx, const float2* X, const float2* spectra, const i
                   int nitems, int F, int D, int B, int N, RowRec* rows, float tie_scale, float* q_out) {
   if (q_out && (nepoch != 1 || nitems != 1 || D != 1)) return set_error(ctx, GACQ_ERR_BAD_ARG, "LDS FFT engine: a row dump takes exactly one row");
   if (!lds_supported(N)) return set_error(ctx, GACQ_ERR_UNSUPPORTED, "LDS FFT engine: N=%d not supported", N);
-  if (N == kBig && !radix16_16k(ctx)) return r32_correlate(ctx, X, spectra, d_items, d_fset, nepoch, nitems, F, D, B, rows, tie_scale, q_out);
   if (N == kBig) {
     const float2* twn;
     int rcb = twiddle_cache(ctx, "W16384_lo", kBig, 1024, &twn);

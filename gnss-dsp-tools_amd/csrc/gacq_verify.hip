@@ -874,7 +874,8 @@ static int r31_64_search(gacq_sig* sig, XSrc d_x, size_t nsamp, int nepoch, int 
   return GACQ_OK;
 }
 
-int verify_search(gacq_sig* sig, XSrc d_x, size_t nsamp, int nepoch, int P, int F, int D, int B, gacq_peak* d_out, float* d_qrow) {
+int verify_search(gacq_sig* sig, const SearchPlan& plan, XSrc d_x, size_t nsamp, int nepoch, int P, int F, int D, int B, gacq_peak* d_out,
+                  float* d_qrow) {
   gacq_ctx* ctx = sig->ctx;
   hipStream_t st = ctx->stream;
   const int n = sig->desc.n, N = sig->N;
@@ -882,10 +883,11 @@ int verify_search(gacq_sig* sig, XSrc d_x, size_t nsamp, int nepoch, int P, int 
   if ((rc = verify_spectra(sig)) != GACQ_OK) return rc;
   const double2* tab;
   if ((rc = nco_table64(ctx, &tab)) != GACQ_OK) return rc;
-  if (N == 4096 && B == 1 && F == 1 && !d_qrow && ctx->opt[GACQ_OPT_FUSED_C128]) {
+  const double2* tw = nullptr;      // N = 4096: the resident transform's twiddles
+  if ((plan.form == Form::C128Fused4k || plan.form == Form::C128Lds4k) && (rc = twiddle64_4096(ctx, &tw)) != GACQ_OK) return rc;
+  switch (plan.form) {
+  case Form::C128Fused4k: {
     // one kernel per search instead of the five-stage pipeline: the row never leaves the workgroup
-    const double2* tw;
-    if ((rc = twiddle64_4096(ctx, &tw)) != GACQ_OK) return rc;
     if ((rc = ensure(ctx, ctx->rows, sizeof(RowRec64) * (size_t)nepoch * P * D)) != GACQ_OK) return rc;
     RowRec64* rows = (RowRec64*)ctx->rows.p;
     // one forward transform per workgroup: amortised over up to 32 items while >= ~1024 workgroups remain (2 resident per CU)
@@ -907,10 +909,8 @@ int verify_search(gacq_sig* sig, XSrc d_x, size_t nsamp, int nepoch, int P, int 
     GACQ_HIP(ctx, hipGetLastError());
     return GACQ_OK;
   }
-  if (N == 4096 && !d_qrow && ctx->opt[GACQ_OPT_FUSED_C128]) {
+  case Form::C128Lds4k: {
     // several blocks or carriers: forward spectra once, then one workgroup per (epoch, Doppler bin, item) over its B rows
-    const double2* tw;
-    if ((rc = twiddle64_4096(ctx, &tw)) != GACQ_OK) return rc;
     const size_t x_epoch_bytes = sizeof(double2) * (size_t)F * D * B * N;
     const int Ec = (int)std::max<size_t>(1, std::min<size_t>((size_t)nepoch, ws_budget(ctx) / std::max<size_t>(1, x_epoch_bytes)));
     if ((rc = ensure(ctx, ctx->X, x_epoch_bytes * Ec)) != GACQ_OK) return rc;
@@ -940,11 +940,14 @@ int verify_search(gacq_sig* sig, XSrc d_x, size_t nsamp, int nepoch, int P, int 
     }
     return GACQ_OK;
   }
-  // N = 4 x 4096 / 16 x 4096: the hand-written split form (one Z' round trip, no rocFFT plan); GACQ_OPT_FUSED_C128 = 0 keeps the pipeline
-  if (ctx->opt[GACQ_OPT_FUSED_C128] && N == 4 * f64::kN) return split64_search<4>(sig, d_x, nsamp, nepoch, P, F, D, B, d_out, d_qrow, tab);
-  if (ctx->opt[GACQ_OPT_FUSED_C128] && N == 16 * f64::kN) return split64_search<16>(sig, d_x, nsamp, nepoch, P, F, D, B, d_out, d_qrow, tab);
+  // N = 4 x 4096 / 16 x 4096: the hand-written split form (one Z' round trip, no rocFFT plan)
+  case Form::C128Split:
+    return N == 4 * f64::kN ? split64_search<4>(sig, d_x, nsamp, nepoch, P, F, D, B, d_out, d_qrow, tab)
+                            : split64_search<16>(sig, d_x, nsamp, nepoch, P, F, D, B, d_out, d_qrow, tab);
   // N = 31 x M with M in rocFFT's native radices (61380, 30690): the prime stays out of rocFFT (no Bluestein)
-  if (ctx->opt[GACQ_OPT_FUSED_C128] && (N == 61380 || N == 30690)) return r31_64_search(sig, d_x, nsamp, nepoch, P, F, D, B, d_out, d_qrow, tab);
+  case Form::C128R31: return r31_64_search(sig, d_x, nsamp, nepoch, P, F, D, B, d_out, d_qrow, tab);
+  default: break;      // Form::C128Rocfft
+  }
   const size_t x_epoch_bytes = sizeof(double2) * (size_t)F * D * B * N;
   const int Ec = (int)std::max<size_t>(1, std::min<size_t>((size_t)nepoch, ws_budget(ctx) / std::max<size_t>(1, x_epoch_bytes)));
   if ((rc = ensure(ctx, ctx->X, x_epoch_bytes * Ec)) != GACQ_OK) return rc;
