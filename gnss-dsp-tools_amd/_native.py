@@ -168,6 +168,14 @@ SYMBOLS = {
     "gacq_correlate_batch_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int, c_int_p,
                                                 c_double_p, c_double_p, c_double_p, ctypes.c_int, c_double_p]),
     "gacq_mix_int8_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
+    # device-resident tracking loops (trackloop.py): spec / record / state structs are passed as plain addresses
+    "gacq_track_open": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "gacq_track_run_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                          ctypes.c_int, c_int_p, c_int_p]),
+    "gacq_track_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "gacq_track_close": (None, [ctypes.c_void_p]),
+    "gacq_track_debug_mix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_double, ctypes.c_void_p]),
     "gacq_stream_probe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, c_double_p]),
     "gacq_stream_create_cu_mask": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     "gacq_stream_destroy": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p]),

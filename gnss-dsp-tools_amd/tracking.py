@@ -3,7 +3,7 @@
 Mirror of the reference's per-signal ``<module>.correlate(x, prn, chips, frac, incr, c[, boc11])``
 (gnsstools/gps/ca.py:120-128 and the BOC / CBOC / TMBOC / RZ variants), evaluated for many (PRN, start phase,
 rate) triples over one block of samples in a single launch -- e.g. early/prompt/late of every tracked satellite.
-The feedback loops themselves (track-*.py) are sequential and are not part of this package."""
+The feedback loops themselves (track-*.py) run on the device in trackloop.py."""
 import numpy as np
 
 from . import _native as nat

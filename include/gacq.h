@@ -359,6 +359,70 @@ int gacq_correlate_batch_dev(gacq_ctx* ctx, const void* d_x, size_t n, const cha
  * I/Q -> d_out complex64 [nsamp] at the same rate.  Asynchronous on the ctx stream. */
 int gacq_mix_int8_dev(gacq_ctx* ctx, const void* d_iq_int8, size_t nsamp, double fs, double carrier_offset_hz, void* d_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Device-resident tracking loops: the template family of the reference's track-*.py (track-gps-l1.py:33-179 and the scripts that
+ * differ from it only in the constants below), one workgroup per channel walking its own blocks -- offset and carrier wipe-off
+ * (table NCO), early/prompt/late, FLL/PLL/DLL update -- with the state kept on the device between calls.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gacq_track gacq_track;
+
+typedef struct gacq_track_spec {   /* one channel: the script's constants and its command line */
+  const char* code;                /* code module, e.g. "gps.ca" */
+  int prn;                         /* PRN (GLONASS: 0) */
+  int kind;                        /* correlator kind of gacq_correlate_batch (0 plain .. 5 RZ [0,1]) */
+  int subs;                        /* track() calls per outer block: 1, 4, 10 or 20 */
+  int fixed_pll;                   /* 1: mode is PLL from the start and never switches (Xona) */
+  int glonass;                     /* 1: offset phase advances by n*fm (fm = -(coffset + step*chan)/fs), else by -(n*coffset)/fs */
+  int pad;
+  double fs;                       /* sample rate, Hz */
+  double period;                   /* seconds per outer block (0.001, 0.004, 0.01, 0.020) */
+  double rate;                     /* its inverse as the script writes it (1000.0, 250.0, 100.0, 50.0) */
+  double ratio;                    /* carrier / code frequency ratio of cf = (code_f + carrier_f/ratio)/fs */
+  double spacing;                  /* early/late offset, chips */
+  double chip_rate;                /* initial code_f */
+  double fll_k_wide, fll_k_narrow, pll_k1, pll_k2, dll_k1, dll_k2;
+  double coffset;                  /* carrier_offset argument, Hz */
+  double fm;                       /* GLONASS: -(coffset + step*chan)/fs; otherwise unused */
+  double code_offset;              /* code_offset argument, chips, in [0, L) */
+  double doppler;                  /* doppler argument, Hz */
+  double carrier_phase;            /* initial carrier phase, cycles */
+  double dwell_wide, dwell_narrow; /* --loop-dwells, records (0, 0 with --carrier-phase) */
+} gacq_track_spec;
+
+typedef struct gacq_track_record { /* one track() call: what the script prints */
+  double p_re, p_im, carrier_f, code_f, early, prompt, late, code_p, carrier_p;
+  long long block, code_cyc, carrier_cyc, samp;
+} gacq_track_record;
+
+typedef struct gacq_track_chstate {  /* a channel's loop state between calls */
+  double code_p, code_f, carrier_p, carrier_f, prompt1_re, prompt1_im, carrier_e1, code_e1, coffset_phase;
+  long long pos;                   /* next block's first sample in the channel's recording */
+  long long block, samp, code_cyc, carrier_cyc;
+  int mode;                        /* 0 FLL_WIDE, 1 FLL_NARROW, 2 PLL (of the last record) */
+  int status;                      /* GACQ_TRACK_* */
+  int last_records;                /* records the last gacq_track_run_dev call wrote */
+  int pad;
+} gacq_track_chstate;
+
+#define GACQ_TRACK_RUNNING 0
+#define GACQ_TRACK_BAD_BLOCK 1    /* the block length came out NaN or below one sample: the channel stopped */
+#define GACQ_TRACK_BAD_PHASE 2    /* an NCO phase or rate is not finite or out of the fixed-point range: the channel stopped */
+
+/* K channels; every spec is checked before anything is allocated, and the code-boundary alignment of the script is done here. */
+int gacq_track_open(gacq_ctx* ctx, const gacq_track_spec* specs, int K, gacq_track** out);
+/* One launch on the ctx stream: channel k's samples d_x[k] (device, interleaved int8 I/Q) are samples [base[k], base[k] + avail[k])
+ * of its recording; each channel writes at most max_records records (whole outer blocks; a record is one track() call, 1 ms of
+ * signal), stopping at the first block those samples cannot fill.  base[k] must not lie beyond the channel's next block.
+ * records: [K][rec_cap] (subs <= max_records <= rec_cap), counts[K] records written, status[K] GACQ_TRACK_*.  Synchronous. */
+int gacq_track_run_dev(gacq_track* tr, const void* const* d_x, const long long* base, const long long* avail, int max_records,
+                       gacq_track_record* records, int rec_cap, int* counts, int* status);
+int gacq_track_state(gacq_track* tr, int k, gacq_track_chstate* out);
+void gacq_track_close(gacq_track* tr);
+/* The loop's two wipe-offs alone, for checking them bit for bit: d_out[k] (complex64) = nco.mix(nco.mix(x, f_offset, p_offset),
+ * f_carrier, p_carrier)[k] for the n int8 I/Q samples at d_iq_int8, computed by the loop's own device helpers.  Synchronous. */
+int gacq_track_debug_mix(gacq_ctx* ctx, const void* d_iq_int8, size_t n, double f_offset, double p_offset, double f_carrier,
+                         double p_carrier, void* d_out);
+
 /* Per-stage GPU time from HIP events recorded on the launch stream (profiling aid for bench.py).
  * Stages: 0 mix/forward, 1 forward FFT (rocFFT), 2 conj-multiply, 3 inverse FFT (rocFFT),
  *         4 magnitude/peak reduce, 5 best-over-Doppler, 6 fused correlate kernel (LDS FFT). */
