@@ -174,6 +174,12 @@ SYMBOLS = {
                                           ctypes.c_int, c_int_p, c_int_p]),
     "gacq_track_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "gacq_track_close": (None, [ctypes.c_void_p]),
+    # long-code tracking loops (longtrack.py): the same structs
+    "gacq_longtrack_open": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "gacq_longtrack_run_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_int, c_int_p, c_int_p]),
+    "gacq_longtrack_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "gacq_longtrack_close": (None, [ctypes.c_void_p]),
     "gacq_track_debug_mix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                             ctypes.c_double, ctypes.c_void_p]),
     "gacq_stream_probe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, c_double_p]),

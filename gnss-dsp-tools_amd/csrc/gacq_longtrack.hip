@@ -1,20 +1,24 @@
-// Device-resident tracking loops: the template family of the reference's track-*.py scripts (track-gps-l1.py:33-94 and the 27
-// scripts that differ from it only in constants), one workgroup per channel, each walking its own blocks with no host round trip.
+// Device-resident tracking loops for the long-code scripts: track-gps-l2cl.py (767 250-chip RZ code, 1.5 s outer block in 1500
+// track() calls) and track-glonass-l1-p.py / -l2-p.py (5 110 000-chip code, 1 s outer block in 1000 calls), one workgroup per
+// channel.  Their track() and main loop differ from the template (gacq_trackloop.hip) only in constants and in dropping the cycle
+// counters, so the arithmetic here is the template's, step for step:
+//   - the offset wipe-off over the whole outer block and the carrier wipe-off per sub-block, both the 50-bit fixed-point table NCO
+//     of gnsstools/nco.py:30-41, each product rounded to complex64; the offset phase is closed form over the sample's index
+//     within the outer block (dpo + k*dfo mod 2^64);
+//   - early / prompt / late with the closed-form phases floor(fma(incr, i, cp0)) mod L, each term rounded before it is summed,
+//     and the template's fixed-order reduction;
+//   - lane 0 runs the FLL / PLL / DLL update in the script's order and writes one record per track() call; the mode switches are
+//     checked once per outer block against the record counter.
+// What is new is the chip source.  The code table stays in device memory (table_cache's "chips:<code>:<prn>", shared with the
+// long-code search); per sub-block the workgroup stages the chips it will touch -- from floor(cp0 of early) to the last chip late
+// reaches, wrapped mod L -- into an LDS window and indexes it with exact integer offsets, which give the same chip as the
+// template's floor(pos) mod L.  A sub-block whose span exceeds the window (a code rate far off) stops the channel with
+// GACQ_TRACK_BAD_WINDOW before it is correlated; no record is ever computed from a partial window.
 //
-// Per outer block (one code period, or 4 / 10 / 20 of them for E1B/E1C, L1C/B1C, L2CM) the workgroup
-//   1. takes the block length from code_p, exactly as the script writes it: int(fs*period*(L-code_p)/L) (or 2L-code_p);
-//   2. mixes the offset wipe-off over the whole block and, per sub-block, the carrier wipe-off -- both the 50-bit fixed-point
-//      table NCO of gnsstools/nco.py:30-41, each product a complex128 multiply (complex128 table) rounded to complex64, as the
-//      reference stores it into its c8 array;
-//   3. forms early / prompt / late with the closed-form phases of gacq_tracking.hip (floor(fma(incr, i, cp0)) mod L), the chip
-//      weight in fp64 as the reference's complex64 x float64 product has it, and sums them in fp64;
-//   4. lets lane 0 run the FLL / PLL / DLL update of the script in the script's own evaluation order, and writes one record.
-// The state lives in device memory between launches; a launch stops a channel at the first block its samples cannot fill, after
-// max_records records, or -- with a status code -- at a block length that is NaN or not positive or an NCO phase out of range.
 // Nothing waits on another workgroup and every loop is bounded by max_records and by the samples given.
 //
-// Contraction is off for the whole file: the loop update must round every product and sum on its own (a*b+c as the script has
-// it); the phases that are fused on purpose are spelled as fma().
+// Contraction is off for the whole file, as in gacq_trackloop.hip: every product and sum is rounded on its own, and the phases that
+// are fused on purpose are spelled as fma().
 #pragma clang fp contract(off)
 
 #include "gacq_common.h"
@@ -24,6 +28,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -31,19 +36,33 @@ using namespace gacq;
 
 namespace {
 
-constexpr int kTlBlock = 256;
-constexpr int kMaxChips = 10240;              // the longest in-scope code is 10230 chips
+constexpr int kLtBlock = 256;
+constexpr int kMaxSubs = 1500;                // track-gps-l2cl.py: 1500 calls per outer block
+// LDS chip window: a sub-block spans at most 1.5 code-ms (n = fs*period*(2L-code_p)/L with code_p just above L/2) -- 767 chips
+// for L2CL, 7665 for GLONASS P -- plus the early/late spacing on each side
+constexpr int kWinChips = 16384;
 
-__global__ __launch_bounds__(kTlBlock) void track_loop_kernel(const TlSpec* __restrict__ specs, const TlRun* __restrict__ runs,
-                                                              gacq_track_chstate* __restrict__ states, const double2* __restrict__ nco_tab,
-                                                              gacq_track_record* __restrict__ recs, int rec_cap,
-                                                              int max_records) {
+// the chip weight of window chip q = floor(pos) + qoff (the window holds chips base .. base+span-1 mod L, and qoff = off - floor(cp0)
+// maps the correlator's own start chip to its place there) times the RZ half-chip gate; kinds 0 (plain), 4 and 5 (RZ) only
+__device__ __forceinline__ double window_weight(const uint8_t* win, int qoff, int kind, double cp0, double bp0, double incr, double di) {
+  const double pos = fma(incr, di, cp0);
+  double w = win[(int)floor(pos) + qoff] ? -1.0 : 1.0;
+  if (kind != 0) {
+    const int b1 = (int)floor(fma(2.0 * incr, di, bp0)) & 1;
+    w = ((kind == 4) == (b1 == 0)) ? w : 0.0;                                         // rz = [1,0] (kind 4) / [0,1] (kind 5)
+  }
+  return w;
+}
+
+__global__ __launch_bounds__(kLtBlock) void longtrack_kernel(const TlSpec* __restrict__ specs, const TlRun* __restrict__ runs,
+                                                             gacq_track_chstate* __restrict__ states, const double2* __restrict__ nco_tab,
+                                                             gacq_track_record* __restrict__ recs, int rec_cap, int max_records) {
   __shared__ double2 s_tab[kNT];
-  __shared__ uint8_t s_chips[kMaxChips];
-  __shared__ double s_red[6][kTlBlock / 16];
+  __shared__ uint8_t s_win[kWinChips];
+  __shared__ double s_red[6][kLtBlock / 16];
   __shared__ double s_sum[6];
   __shared__ gacq_track_chstate st;
-  __shared__ TlSpec sp;               // read from LDS where used: a copy in registers overflows the SGPR file
+  __shared__ TlSpec sp;
   const int ch = blockIdx.x;
   const int tid = threadIdx.x;
   const TlRun run = runs[ch];
@@ -51,25 +70,21 @@ __global__ __launch_bounds__(kTlBlock) void track_loop_kernel(const TlSpec* __re
     st = states[ch];
     sp = specs[ch];
   }
-  for (int k = tid; k < kNT; k += kTlBlock) s_tab[k] = nco_tab[k];
-  __syncthreads();
-  for (int k = tid; k < sp.L; k += kTlBlock) s_chips[k] = sp.chips[k];
+  for (int k = tid; k < kNT; k += kLtBlock) s_tab[k] = nco_tab[k];
   __syncthreads();
   const long L = sp.L;
   const double Ld = (double)sp.L;
-  const double inv_l = 1.0 / Ld;
   const double fs = sp.fs;
   int nrec = 0;
-  // every record is one track() call (1 ms of signal in every template script): an outer block runs only if all its records fit
   while (nrec + sp.subs <= max_records) {
     if (st.status != 0) break;
-    // mode switches, once per outer block against the record counter (track-gps-l1.py:156-159)
+    // mode switches, once per outer block against the record counter (track-gps-l2cl.py:147-150)
     const int mode = sp.fixed_pll ? kModePll
                    : ((double)st.block >= sp.dwell_wide + sp.dwell_narrow ? kModePll
                    : ((double)st.block >= sp.dwell_wide ? kModeFllNarrow : st.mode));
     const double code_p = st.code_p;
     const double nf = code_p < Ld / 2 ? (fs * sp.period * (Ld - code_p)) / Ld : (fs * sp.period * (2 * Ld - code_p)) / Ld;
-    if (!(nf >= 1.0) || !(nf < 4.0e15)) {            // NaN, or int(nf) <= 0: nothing the reference could read sensibly
+    if (!(nf >= 1.0) || !(nf < 4.0e15)) {
       __syncthreads();
       if (tid == 0) st.status = GACQ_TRACK_BAD_BLOCK;
       __syncthreads();
@@ -80,6 +95,7 @@ __global__ __launch_bounds__(kTlBlock) void track_loop_kernel(const TlSpec* __re
     const long long dpo = nco_fixed(st.coffset_phase);
     const int8_t* xb = run.x + 2 * (st.pos - run.base);
     for (int j = 0; j < sp.subs; j++) {
+      // a,b = int(j*n/subs),int((j+1)*n/subs): j*n < 2^53, so the true division is one correctly rounded fp64 division
       const long long a = (long long)((double)((long long)j * n) / (double)sp.subs);
       const long long b = (long long)((double)((long long)(j + 1) * n) / (double)sp.subs);
       const long long m = b - a;
@@ -93,15 +109,38 @@ __global__ __launch_bounds__(kTlBlock) void track_loop_kernel(const TlSpec* __re
         break;
       }
       const long long dpc = nco_fixed(carrier_p), dfc = nco_fixed(fc);
-      double cp0[3], bp0[3], bp60[3];
+      double cp0[3], bp0[3];
+      long fl0[3];
       for (int t = 0; t < 3; t++) {
         const double frac = t == 0 ? cp_code - sp.spacing : (t == 1 ? cp_code : cp_code + sp.spacing);
         cp0[t] = pymod(frac, Ld);
         bp0[t] = pymod(2.0 * frac, 2.0);
-        bp60[t] = pymod(12.0 * frac, 2.0);
+        fl0[t] = (long)floor(cp0[t]);
       }
+      // the window starts at early's first chip; correlator t's first chip sits off[t] = (fl0[t] - base) mod L into it, and its
+      // last one -- the phases are non-decreasing in i for cf >= 0 -- at the same fma() for i = m - 1
+      const long base = fl0[0];
+      long off[3], span = 0;
+      for (int t = 0; t < 3; t++) {
+        off[t] = fl0[t] - base;
+        if (off[t] < 0) off[t] += L;
+        if (m > 0) span = std::max(span, (long)floor(fma(cf, (double)(m - 1), cp0[t])) - fl0[t] + off[t] + 1);
+      }
+      if (!(cf >= 0.0) || span > kWinChips) {
+        __syncthreads();
+        if (tid == 0) st.status = GACQ_TRACK_BAD_WINDOW;
+        __syncthreads();
+        break;
+      }
+      for (long q = tid; q < span; q += kLtBlock) {
+        long g = base + q;
+        if (g >= L) g %= L;
+        s_win[q] = sp.chips[g];
+      }
+      __syncthreads();
+      const int qoff[3] = {(int)(off[0] - fl0[0]), (int)(off[1] - fl0[1]), (int)(off[2] - fl0[2])};
       double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      for (long long i = tid; i < m; i += kTlBlock) {
+      for (long long i = tid; i < m; i += kLtBlock) {
         const long long k = a + i;
         const unsigned long long po = (unsigned long long)dpo + (unsigned long long)k * (unsigned long long)sp.dfo;
         const unsigned long long pc = (unsigned long long)dpc + (unsigned long long)i * (unsigned long long)dfc;
@@ -110,13 +149,12 @@ __global__ __launch_bounds__(kTlBlock) void track_loop_kernel(const TlSpec* __re
         const double vr = (double)v.x, vi = (double)v.y, di = (double)i;
 #pragma unroll
         for (int t = 0; t < 3; t++) {
-          const double w = chip_weight(s_chips, L, inv_l, sp.kind, cp0[t], bp0[t], bp60[t], cf, di);
+          const double w = window_weight(s_win, qoff[t], sp.kind, cp0[t], bp0[t], cf, di);
           acc[2 * t] = acc[2 * t] + vr * w;                                       // p += x[i]*w: product rounded, then the sum
           acc[2 * t + 1] = acc[2 * t + 1] + vi * w;
         }
       }
-      // row sums by DPP (lanes 0, 16, 32, 48 of each wave), then through LDS: reading the rows out with v_readlane would hold the six
-      // sums in 48 SGPRs at once, more than the scalar file has left
+      // the template's reduction: DPP within rows of 16, then the 16 row sums in a fixed order
 #pragma unroll
       for (int t = 0; t < 6; t++) {
         double v = acc[t];
@@ -129,9 +167,9 @@ __global__ __launch_bounds__(kTlBlock) void track_loop_kernel(const TlSpec* __re
       if ((tid & 15) == 0)
         for (int t = 0; t < 6; t++) s_red[t][tid >> 4] = acc[t];
       __syncthreads();
-      if (tid < 6) {                    // one lane per sum, in a fixed order
+      if (tid < 6) {
         double s = 0.0;
-        for (int w = 0; w < kTlBlock / 64; w++)
+        for (int w = 0; w < kLtBlock / 64; w++)
           s = s + ((s_red[tid][4 * w] + s_red[tid][4 * w + 1]) + (s_red[tid][4 * w + 2] + s_red[tid][4 * w + 3]));
         s_sum[tid] = s;
       }
@@ -140,12 +178,12 @@ __global__ __launch_bounds__(kTlBlock) void track_loop_kernel(const TlSpec* __re
         double p[6];
         for (int t = 0; t < 6; t++) p[t] = s_sum[t];
         const double md = (double)m;
-        // carrier NCO phase (track-gps-l1.py:36-42)
+        // carrier NCO phase (track-gps-l2cl.py:35-37): np.mod only; the cycle count is kept for the record, the script drops it
         double cpn = carrier_p - (md * carrier_f) / fs;
         const double ct = pymod(cpn, 1.0);
         st.carrier_cyc += (long long)rint(cpn - ct);
         st.carrier_p = ct;
-        // carrier loop (:52-70)
+        // carrier loop (:41-65)
         double cfn = carrier_f;
         const double pr = p[2], pi_ = p[3];
         if (mode == kModePll) {
@@ -159,7 +197,7 @@ __global__ __launch_bounds__(kTlBlock) void track_loop_kernel(const TlSpec* __re
           st.prompt1_im = pi_;
         }
         st.carrier_f = cfn;
-        // code loop (:74-92)
+        // code loop (:69-84)
         const double early = hypot(p[0], p[1]), prompt = hypot(pr, pi_), late = hypot(p[4], p[5]);
         const double e = (late + early) == 0.0 ? 0.0 : (late - early) / (late + early);
         st.code_f = code_f + sp.dll_k1 * e + sp.dll_k2 * (e - st.code_e1);
@@ -183,7 +221,7 @@ __global__ __launch_bounds__(kTlBlock) void track_loop_kernel(const TlSpec* __re
     }
     if (st.status != 0) break;
     if (tid == 0) {
-      // offset wipe-off phase, the script's own expression (track-gps-l1.py:171-173; GLONASS adds n*fm instead)
+      // offset wipe-off phase (track-gps-l2cl.py:162-164; GLONASS P adds n*fm, track-glonass-l1-p.py:161-164)
       const double nd = (double)n;
       const double cph = sp.glonass ? st.coffset_phase + nd * sp.fm : st.coffset_phase - (nd * sp.coffset) / fs;
       st.coffset_phase = pymod(cph, 1.0);
@@ -193,100 +231,54 @@ __global__ __launch_bounds__(kTlBlock) void track_loop_kernel(const TlSpec* __re
   }
   __syncthreads();
   if (tid == 0) {
-    st.last_records = nrec;            // the count travels in the state: one pointer less held across the whole kernel
+    st.last_records = nrec;
     states[ch] = st;
   }
 }
 
-// The two wipe-offs of track_loop_kernel alone, over n samples (offset NCO at sample k, carrier NCO at sample k): the same helpers and
-// index arithmetic, so the complex64 values it writes are what the correlators of the loop see (gacq_track_debug_mix)
-__global__ __launch_bounds__(kTlBlock) void track_mix_kernel(const int8_t* __restrict__ x, long long n, long long dpo, long long dfo,
-                                                             long long dpc, long long dfc, const double2* __restrict__ nco_tab,
-                                                             float2* __restrict__ out) {
-  for (long long k = (long long)blockIdx.x * kTlBlock + threadIdx.x; k < n; k += (long long)gridDim.x * kTlBlock) {
-    const unsigned long long po = (unsigned long long)dpo + (unsigned long long)k * (unsigned long long)dfo;
-    const unsigned long long pc = (unsigned long long)dpc + (unsigned long long)k * (unsigned long long)dfc;
-    float2 v = mix_c64(make_float2((float)x[2 * k], (float)x[2 * k + 1]), nco_tab[(po >> 50) & (kNT - 1)]);
-    out[k] = mix_c64(v, nco_tab[(pc >> 50) & (kNT - 1)]);
-  }
-}
-
-__global__ void nco_fixed_kernel(double p0, double f0, double p1, double f1, long long* out) {
-  out[0] = nco_fixed(p0);
-  out[1] = nco_fixed(f0);
-  out[2] = nco_fixed(p1);
-  out[3] = nco_fixed(f1);
-}
-
 }  // namespace
 
-extern "C" int gacq_track_debug_mix(gacq_ctx* ctx, const void* d_iq_int8, size_t n, double f_offset, double p_offset, double f_carrier,
-                                    double p_carrier, void* d_out) {
-  if (!ctx || !d_iq_int8 || !d_out || n == 0 || n > ((size_t)1 << 40))
-    return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_track_debug_mix: bad argument");
-  for (double v : {f_offset, p_offset, f_carrier, p_carrier})
-    if (!(std::fabs(v) < 7.0)) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_track_debug_mix: NCO frequency or phase out of range");
-  GACQ_DEVICE(ctx);
-  const double2* tab = nullptr;
-  int rc = nco_table(ctx, &tab);
-  if (rc != GACQ_OK) return rc;
-  // the fixed-point phases exactly as the loop forms them: on the device
-  long long* d_fix = nullptr;
-  GACQ_HIP(ctx, hipMalloc(&d_fix, 4 * sizeof(long long)));
-  long long fix[4];
-  hipLaunchKernelGGL(nco_fixed_kernel, dim3(1), dim3(1), 0, ctx->stream, p_offset, f_offset, p_carrier, f_carrier, d_fix);
-  hipError_t e = hipMemcpyAsync(fix, d_fix, sizeof(fix), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_fix);
-  if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_track_debug_mix: %s", hipGetErrorString(e));
-  const unsigned grid = (unsigned)std::min<size_t>((n + kTlBlock - 1) / kTlBlock, 4096);
-  hipLaunchKernelGGL(track_mix_kernel, dim3(grid), dim3(kTlBlock), 0, ctx->stream, (const int8_t*)d_iq_int8, (long long)n, fix[0], fix[1],
-                     fix[2], fix[3], tab, (float2*)d_out);
-  GACQ_HIP(ctx, hipGetLastError());
-  GACQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return GACQ_OK;
-}
-
-struct gacq_track {
+struct gacq_longtrack {
   gacq_ctx* ctx = nullptr;
   int K = 0;
   int subs_max = 1;
-  std::vector<TlSpec> specs;
-  std::vector<gacq_track_chstate> init;
   DevBuf d_specs, d_runs, d_states, d_recs;
   const double2* d_tab = nullptr;
 };
 
-extern "C" int gacq_track_open(gacq_ctx* ctx, const gacq_track_spec* specs, int K, gacq_track** out) {
-  if (!ctx || !out) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_track_open: NULL argument");
+extern "C" int gacq_longtrack_open(gacq_ctx* ctx, const gacq_track_spec* specs, int K, gacq_longtrack** out) {
+  if (!ctx || !out) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_open: NULL argument");
   *out = nullptr;
-  if (!specs || K <= 0) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_track_open: need at least one channel (K = %d)", K);
+  if (!specs || K <= 0) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_open: need at least one channel (K = %d)", K);
   std::vector<TlSpec> ts(K);
   std::vector<gacq_track_chstate> init(K);
   std::vector<std::string> keys(K);
-  std::vector<std::vector<uint8_t>> chips(K);
+  std::map<std::string, std::vector<uint8_t>> chips;      // tables not yet in the context's cache, one per code and PRN
   int subs_max = 1;
   for (int k = 0; k < K; k++) {
     const gacq_track_spec& s = specs[k];
-    if (!s.code) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_track_open: channel %d has no code", k);
+    if (!s.code) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_open: channel %d has no code", k);
     const int L = gacq_code_length(s.code);
-    if (L < 0) return set_error(ctx, GACQ_ERR_UNKNOWN_CODE, "gacq_track_open: channel %d: unknown code '%s'", k, s.code);
-    if (L > kMaxChips) return set_error(ctx, GACQ_ERR_UNSUPPORTED, "gacq_track_open: channel %d: code '%s' is longer than %d chips", k, s.code, kMaxChips);
+    if (L < 0) return set_error(ctx, GACQ_ERR_UNKNOWN_CODE, "gacq_longtrack_open: channel %d: unknown code '%s'", k, s.code);
     const bool fin = std::isfinite(s.fs) && std::isfinite(s.period) && std::isfinite(s.rate) && std::isfinite(s.ratio) &&
                      std::isfinite(s.spacing) && std::isfinite(s.coffset) && std::isfinite(s.fm) && std::isfinite(s.code_offset) &&
                      std::isfinite(s.doppler) && std::isfinite(s.carrier_phase) && std::isfinite(s.chip_rate);
-    if (!fin || !(s.fs > 0.0)) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_track_open: channel %d: bad sample rate or parameter", k);
+    if (!fin || !(s.fs > 0.0)) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_open: channel %d: bad sample rate or parameter", k);
     if (!(s.code_offset >= 0.0 && s.code_offset < (double)L))
-      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_track_open: channel %d: code offset %g outside [0, %d)", k, s.code_offset, L);
-    if (s.kind < 0 || s.kind > 5 || s.subs < 1 || s.subs > 64 || !(s.period > 0.0) || !(s.rate > 0.0) || s.ratio == 0.0 || !(s.spacing >= 0.0))
-      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_track_open: channel %d: bad tracker parameters", k);
+      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_open: channel %d: code offset %g outside [0, %d)", k, s.code_offset, L);
+    if (!(s.kind == 0 || s.kind == 4 || s.kind == 5) || s.subs < 1 || s.subs > kMaxSubs || !(s.period > 0.0) || !(s.rate > 0.0) ||
+        s.ratio == 0.0 || !(s.spacing >= 0.0) || !(s.spacing < 0.25 * kWinChips))
+      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_open: channel %d: bad tracker parameters", k);
     const double fo = s.glonass ? s.fm : -s.coffset / s.fs;
     if (!(std::fabs(fo) < 7.0) || !(std::fabs(s.carrier_phase) < 7.0) || !(std::fabs(s.doppler / s.fs) < 7.0))
-      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_track_open: channel %d: NCO frequency or phase out of range", k);
-    chips[k].resize(L);
-    const int rc = gacq_code_chips(s.code, s.prn, chips[k].data(), L);
-    if (rc < 0) return set_error(ctx, rc, "gacq_track_open: channel %d: no PRN %d in '%s'", k, s.prn, s.code);
+      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_open: channel %d: NCO frequency or phase out of range", k);
     keys[k] = std::string("chips:") + s.code + ":" + std::to_string(s.prn);
+    if (!ctx->tables.count(keys[k]) && !chips.count(keys[k])) {
+      std::vector<uint8_t> c(L);
+      const int rc = gacq_code_chips(s.code, s.prn, c.data(), L);
+      if (rc < 0) return set_error(ctx, rc, "gacq_longtrack_open: channel %d: no PRN %d in '%s'", k, s.prn, s.code);
+      chips.emplace(keys[k], std::move(c));
+    }
     TlSpec& t = ts[k];
     t.L = L; t.kind = s.kind; t.subs = s.subs; t.fixed_pll = s.fixed_pll ? 1 : 0; t.glonass = s.glonass ? 1 : 0; t.pad = 0;
     t.fs = s.fs; t.period = s.period; t.ratio = s.ratio; t.spacing = s.spacing;
@@ -294,7 +286,8 @@ extern "C" int gacq_track_open(gacq_ctx* ctx, const gacq_track_spec* specs, int 
     t.coffset = s.coffset; t.fm = s.fm;
     t.dfo = (long long)std::floor(fo * kTwo60);
     t.dwell_wide = s.dwell_wide; t.dwell_narrow = s.dwell_narrow;
-    // alignment with the code boundary (track-gps-l1.py:141-143), on the host: n = int(fs*period*((L-code_offset)/L))
+    // alignment with the code boundary (track-gps-l2cl.py:133-136), on the host: n = int(fs*period*((L-code_offset)/L)),
+    // code_offset += n*rate*L/fs
     const long long n0 = (long long)(s.fs * s.period * (((double)L - s.code_offset) / (double)L));
     gacq_track_chstate& g = init[k];
     std::memset(&g, 0, sizeof(g));
@@ -307,14 +300,15 @@ extern "C" int gacq_track_open(gacq_ctx* ctx, const gacq_track_spec* specs, int 
     subs_max = std::max(subs_max, s.subs);
   }
   GACQ_DEVICE(ctx);
-  gacq_track* h = new gacq_track();
+  gacq_longtrack* h = new gacq_longtrack();
   h->ctx = ctx;
   h->K = K;
   h->subs_max = subs_max;
   int rc = GACQ_OK;
   for (int k = 0; k < K && rc == GACQ_OK; k++) {
     const void* d = nullptr;
-    rc = table_cache(ctx, keys[k], chips[k].data(), chips[k].size(), &d);
+    auto it = chips.find(keys[k]);
+    rc = table_cache(ctx, keys[k], it == chips.end() ? nullptr : it->second.data(), it == chips.end() ? 0 : it->second.size(), &d);
     ts[k].chips = (const uint8_t*)d;
   }
   if (rc == GACQ_OK) rc = nco_table(ctx, &h->d_tab);
@@ -322,25 +316,23 @@ extern "C" int gacq_track_open(gacq_ctx* ctx, const gacq_track_spec* specs, int 
   if (rc == GACQ_OK) rc = ensure(ctx, h->d_runs, sizeof(TlRun) * K);
   if (rc == GACQ_OK) rc = ensure(ctx, h->d_states, sizeof(gacq_track_chstate) * K);
   if (rc == GACQ_OK && hipMemcpy(h->d_specs.p, ts.data(), sizeof(TlSpec) * K, hipMemcpyHostToDevice) != hipSuccess)
-    rc = set_error(ctx, GACQ_ERR_HIP, "gacq_track_open: upload failed");
+    rc = set_error(ctx, GACQ_ERR_HIP, "gacq_longtrack_open: upload failed");
   if (rc == GACQ_OK && hipMemcpy(h->d_states.p, init.data(), sizeof(gacq_track_chstate) * K, hipMemcpyHostToDevice) != hipSuccess)
-    rc = set_error(ctx, GACQ_ERR_HIP, "gacq_track_open: upload failed");
+    rc = set_error(ctx, GACQ_ERR_HIP, "gacq_longtrack_open: upload failed");
   if (rc != GACQ_OK) {
-    gacq_track_close(h);
+    gacq_longtrack_close(h);
     return rc;
   }
-  h->specs = std::move(ts);
-  h->init = std::move(init);
   *out = h;
   return GACQ_OK;
 }
 
-extern "C" int gacq_track_run_dev(gacq_track* h, const void* const* d_x, const long long* base, const long long* avail, int max_records,
-                                  gacq_track_record* recs, int rec_cap, int* counts, int* status) {
+extern "C" int gacq_longtrack_run_dev(gacq_longtrack* h, const void* const* d_x, const long long* base, const long long* avail,
+                                      int max_records, gacq_track_record* recs, int rec_cap, int* counts, int* status) {
   if (!h) return GACQ_ERR_BAD_ARG;
   gacq_ctx* ctx = h->ctx;
   if (!d_x || !base || !avail || !recs || !counts || !status || max_records < h->subs_max || rec_cap < max_records)
-    return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_track_run_dev: bad argument (need %d <= max_records <= rec_cap)", h->subs_max);
+    return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_run_dev: bad argument (need %d <= max_records <= rec_cap)", h->subs_max);
   const int K = h->K;
   std::vector<gacq_track_chstate> now(K);
   GACQ_DEVICE(ctx);
@@ -349,11 +341,11 @@ extern "C" int gacq_track_run_dev(gacq_track* h, const void* const* d_x, const l
   GACQ_HIP(ctx, hipStreamSynchronize(stream));
   std::vector<TlRun> runs(K);
   for (int k = 0; k < K; k++) {
-    if (!d_x[k] || base[k] < 0 || avail[k] < 0) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_track_run_dev: channel %d: bad samples", k);
-    // the samples handed over must start at or before the channel's next block
+    if (!d_x[k] || base[k] < 0 || avail[k] < 0)
+      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_run_dev: channel %d: bad samples", k);
     if (base[k] > now[k].pos)
-      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_track_run_dev: channel %d: samples start at %lld, the next block at %lld", k, base[k],
-                       now[k].pos);
+      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_run_dev: channel %d: samples start at %lld, the next block at %lld", k,
+                       base[k], now[k].pos);
     runs[k].x = (const int8_t*)d_x[k];
     runs[k].base = base[k];
     runs[k].end = base[k] + avail[k];
@@ -361,30 +353,35 @@ extern "C" int gacq_track_run_dev(gacq_track* h, const void* const* d_x, const l
   int rc;
   if ((rc = ensure(ctx, h->d_recs, sizeof(gacq_track_record) * (size_t)K * rec_cap)) != GACQ_OK) return rc;
   GACQ_HIP(ctx, hipMemcpyAsync(h->d_runs.p, runs.data(), sizeof(TlRun) * K, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(track_loop_kernel, dim3((unsigned)K), dim3(kTlBlock), 0, stream, (const TlSpec*)h->d_specs.p, (const TlRun*)h->d_runs.p,
+  hipLaunchKernelGGL(longtrack_kernel, dim3((unsigned)K), dim3(kLtBlock), 0, stream, (const TlSpec*)h->d_specs.p, (const TlRun*)h->d_runs.p,
                      (gacq_track_chstate*)h->d_states.p, h->d_tab, (gacq_track_record*)h->d_recs.p, rec_cap, max_records);
   GACQ_HIP(ctx, hipGetLastError());
   GACQ_HIP(ctx, hipMemcpyAsync(now.data(), h->d_states.p, sizeof(gacq_track_chstate) * K, hipMemcpyDeviceToHost, stream));
-  GACQ_HIP(ctx, hipMemcpyAsync(recs, h->d_recs.p, sizeof(gacq_track_record) * (size_t)K * rec_cap, hipMemcpyDeviceToHost, stream));
   GACQ_HIP(ctx, hipStreamSynchronize(stream));
+  // only the records written come back: a channel's count is in its state
   for (int k = 0; k < K; k++) {
     status[k] = now[k].status;
     counts[k] = now[k].last_records;
+    if (counts[k] > 0)
+      GACQ_HIP(ctx, hipMemcpyAsync(recs + (size_t)k * rec_cap, (const gacq_track_record*)h->d_recs.p + (size_t)k * rec_cap,
+                                   sizeof(gacq_track_record) * (size_t)counts[k], hipMemcpyDeviceToHost, stream));
   }
+  GACQ_HIP(ctx, hipStreamSynchronize(stream));
   return GACQ_OK;
 }
 
-extern "C" int gacq_track_state(gacq_track* h, int k, gacq_track_chstate* out) {
+extern "C" int gacq_longtrack_state(gacq_longtrack* h, int k, gacq_track_chstate* out) {
   if (!h) return GACQ_ERR_BAD_ARG;
   gacq_ctx* ctx = h->ctx;
-  if (!out || k < 0 || k >= h->K) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_track_state: bad channel %d", k);
+  if (!out || k < 0 || k >= h->K) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_state: bad channel %d", k);
   GACQ_DEVICE(ctx);
-  GACQ_HIP(ctx, hipMemcpyAsync(out, (const gacq_track_chstate*)h->d_states.p + k, sizeof(gacq_track_chstate), hipMemcpyDeviceToHost, ctx->stream));
+  GACQ_HIP(ctx, hipMemcpyAsync(out, (const gacq_track_chstate*)h->d_states.p + k, sizeof(gacq_track_chstate), hipMemcpyDeviceToHost,
+                               ctx->stream));
   GACQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return GACQ_OK;
 }
 
-extern "C" void gacq_track_close(gacq_track* h) {
+extern "C" void gacq_longtrack_close(gacq_longtrack* h) {
   if (!h) return;
   {
     DeviceGuard g(h->ctx->device);

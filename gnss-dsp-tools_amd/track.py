@@ -1,19 +1,29 @@
-"""Command-line drop-in for the template track-*.py scripts, on the GPU:
+"""Command-line drop-in for the track-*.py scripts on the GPU: the template family (trackloop) and the long-code scripts
+gps-l2cl, glonass-l1-p and glonass-l2-p (longtrack):
 
     python -m gnss_dsp_tools_amd.track <name> [--loop-dwells A,B] [--carrier-phase P] FILE FS COFFSET PRN|CHAN DOPPLER CODE_OFFSET
 
 The options are parsed by optparse with interspersed arguments disabled, exactly as the scripts do (track-gps-l1.py:99-136), so
 negative positional values (carrier offset, GLONASS channel, Doppler) and a negative --carrier-phase value behave the same.
-Output: the script's lines ('%d %f ...', 9 or 14 columns), one per track() call, up to the first block the file cannot fill."""
+Output: the script's lines ('%d %f ...', 9 or 14 columns), one per track() call, up to the first outer block the file cannot fill."""
 import optparse
 import sys
 
-from . import trackloop
+from . import longtrack, trackloop
+
+
+def _tracker(name):
+    return trackloop.TRACKERS[name] if name in trackloop.TRACKERS else longtrack.LONG_TRACKERS[name]
+
+
+def names():
+    """Every tracker name the command line accepts."""
+    return sorted(list(trackloop.TRACKERS) + list(longtrack.LONG_TRACKERS))
 
 
 def build_parser(name):
     p = optparse.OptionParser(usage="%s [options] input_filename sample_rate carrier_offset %s doppler code_offset"
-                              % (name, "chan" if trackloop.TRACKERS[name].glonass else "PRN"))
+                              % (name, "chan" if _tracker(name).glonass else "PRN"))
     p.disable_interspersed_args()
     p.add_option("--loop-dwells", default="500,500", help="initial time intervals for wide FLL, then narrow FLL, in milliseconds "
                                                           "(default %default)")
@@ -23,11 +33,11 @@ def build_parser(name):
 
 def parse(name, argv):
     """Channel of one command line (argv after the tracker name), with the script's own argument conversions."""
-    if name not in trackloop.TRACKERS:
-        raise SystemExit("unknown tracker %r; the template family: %s" % (name, " ".join(sorted(trackloop.TRACKERS))))
+    if name not in trackloop.TRACKERS and name not in longtrack.LONG_TRACKERS:
+        raise SystemExit("unknown tracker %r; the trackers: %s" % (name, " ".join(names())))
     options, args = build_parser(name).parse_args(list(argv))
     if len(args) < 6:
-        raise SystemExit("%s: need input_filename sample_rate carrier_offset %s doppler code_offset" % (name, "chan" if trackloop.TRACKERS[name].glonass else "PRN"))
+        raise SystemExit("%s: need input_filename sample_rate carrier_offset %s doppler code_offset" % (name, "chan" if _tracker(name).glonass else "PRN"))
     dwells = tuple(map(float, options.loop_dwells.split(",")))        # util.parse_list_floats
     phase = float(options.carrier_phase) if options.carrier_phase is not None else None
     ch = trackloop.Channel(name, float(args[1]), float(args[2]), int(args[3]), float(args[4]), float(args[5]), dwells, phase)
@@ -36,7 +46,8 @@ def parse(name, argv):
 
 def run(name, argv, out=sys.stdout):
     path, ch = parse(name, argv)
-    _, lines = trackloop.track_file(name, path, ch.fs, ch.coffset, ch.prn, ch.doppler, ch.code_offset, ch.loop_dwells, ch.carrier_phase)
+    mod = longtrack if name in longtrack.LONG_TRACKERS else trackloop
+    _, lines = mod.track_file(name, path, ch.fs, ch.coffset, ch.prn, ch.doppler, ch.code_offset, ch.loop_dwells, ch.carrier_phase)
     for line in lines:
         out.write(line + "\n")
     return lines
@@ -45,7 +56,7 @@ def run(name, argv, out=sys.stdout):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if not argv or argv[0] in ("-h", "--help"):
-        sys.stdout.write(__doc__ + "\ntrackers: " + " ".join(sorted(trackloop.TRACKERS)) + "\n")
+        sys.stdout.write(__doc__ + "\ntrackers: " + " ".join(names()) + "\n")
         return 0
     run(argv[0], argv[1:])
     return 0

@@ -3,7 +3,8 @@
 Every template script runs the same ``track()`` body (track-gps-l1.py:33-94) and the same main loop (:153-179); they differ only in
 the constants of ``TRACKERS``.  ``TrackLoop`` runs K such channels in one launch (csrc/gacq_trackloop.hip, one workgroup per
 channel), each on its own int8 recording resident on the device, and keeps the loop state on the device between calls, so a
-recording can be fed in chunks.  Out of scope (not template scripts): beidou-b2bi/-b2bq (nco.accum), gps-l2cl, glonass-l1-p/-l2-p.
+recording can be fed in chunks.  Not template scripts: gps-l2cl and glonass-l1-p/-l2-p run in longtrack; beidou-b2bi/-b2bq
+(nco.accum) are out of scope.
 """
 import ctypes
 from dataclasses import dataclass

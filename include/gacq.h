@@ -407,6 +407,7 @@ typedef struct gacq_track_chstate {  /* a channel's loop state between calls */
 #define GACQ_TRACK_RUNNING 0
 #define GACQ_TRACK_BAD_BLOCK 1    /* the block length came out NaN or below one sample: the channel stopped */
 #define GACQ_TRACK_BAD_PHASE 2    /* an NCO phase or rate is not finite or out of the fixed-point range: the channel stopped */
+#define GACQ_TRACK_BAD_WINDOW 3   /* long-code loops: a sub-block's code span does not fit the LDS chip window: the channel stopped */
 
 /* K channels; every spec is checked before anything is allocated, and the code-boundary alignment of the script is done here. */
 int gacq_track_open(gacq_ctx* ctx, const gacq_track_spec* specs, int K, gacq_track** out);
@@ -418,6 +419,20 @@ int gacq_track_run_dev(gacq_track* tr, const void* const* d_x, const long long* 
                        gacq_track_record* records, int rec_cap, int* counts, int* status);
 int gacq_track_state(gacq_track* tr, int k, gacq_track_chstate* out);
 void gacq_track_close(gacq_track* tr);
+/* ---------------------------------------------------------------------------------------------
+ * Device-resident tracking loops for the long-code scripts: track-gps-l2cl.py (1500 track() calls per 1.5 s outer block) and
+ * track-glonass-l1-p.py / -l2-p.py (1000 per 1 s).  Same specs, records and states as gacq_track_*, and the same arithmetic; the code
+ * table stays in device memory and each sub-block reads a window of it.  kind 0 or 4 / 5 (RZ), subs <= 1500, any code length.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gacq_longtrack gacq_longtrack;
+
+int gacq_longtrack_open(gacq_ctx* ctx, const gacq_track_spec* specs, int K, gacq_longtrack** out);
+/* As gacq_track_run_dev: whole outer blocks only (subs <= max_records <= rec_cap), status GACQ_TRACK_* (BAD_WINDOW included). */
+int gacq_longtrack_run_dev(gacq_longtrack* tr, const void* const* d_x, const long long* base, const long long* avail, int max_records,
+                           gacq_track_record* records, int rec_cap, int* counts, int* status);
+int gacq_longtrack_state(gacq_longtrack* tr, int k, gacq_track_chstate* out);
+void gacq_longtrack_close(gacq_longtrack* tr);
+
 /* The loop's two wipe-offs alone, for checking them bit for bit: d_out[k] (complex64) = nco.mix(nco.mix(x, f_offset, p_offset),
  * f_carrier, p_carrier)[k] for the n int8 I/Q samples at d_iq_int8, computed by the loop's own device helpers.  Synchronous. */
 int gacq_track_debug_mix(gacq_ctx* ctx, const void* d_iq_int8, size_t n, double f_offset, double p_offset, double f_carrier,
