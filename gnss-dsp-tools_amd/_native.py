@@ -180,6 +180,13 @@ SYMBOLS = {
                                               ctypes.c_void_p, ctypes.c_int, c_int_p, c_int_p]),
     "gacq_longtrack_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "gacq_longtrack_close": (None, [ctypes.c_void_p]),
+    # tracking loops with the chip accumulator (chiptrack.py): the same structs, one accum_after (int64) per channel
+    "gacq_chiptrack_open": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "gacq_chiptrack_run_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_int, c_int_p, c_int_p]),
+    "gacq_chiptrack_state": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "gacq_chiptrack_chips": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "gacq_chiptrack_close": (None, [ctypes.c_void_p]),
     "gacq_track_debug_mix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                             ctypes.c_double, ctypes.c_void_p]),
     "gacq_stream_probe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, c_double_p]),

@@ -3,7 +3,7 @@
 Their ``track()`` and main loop are the template's (trackloop.py) with other constants: a 767 250- or 5 110 000-chip code, a 1.5 s or
 1 s outer block split into 1500 or 1000 ``track()`` calls, ``np.mod`` phases without cycle counters and 9 printed columns.
 ``LongTrackLoop`` runs K such channels in one launch (csrc/gacq_longtrack.hip, one workgroup per channel); the code table stays in
-device memory and each sub-block reads a window of it.  beidou-b2bi/-b2bq (nco.accum) are not covered.
+device memory and each sub-block reads a window of it.  beidou-b2bi/-b2bq (nco.accum) run in chiptrack.
 """
 import ctypes
 

@@ -1,5 +1,6 @@
 """Command-line drop-in for the track-*.py scripts on the GPU: the template family (trackloop) and the long-code scripts
-gps-l2cl, glonass-l1-p and glonass-l2-p (longtrack):
+gps-l2cl, glonass-l1-p and glonass-l2-p (longtrack); beidou-b2bi and beidou-b2bq, which also write track-chips.dat, are handed to
+python -m gnss_dsp_tools_amd.chiptrack:
 
     python -m gnss_dsp_tools_amd.track <name> [--loop-dwells A,B] [--carrier-phase P] FILE FS COFFSET PRN|CHAN DOPPLER CODE_OFFSET
 
@@ -9,7 +10,7 @@ Output: the script's lines ('%d %f ...', 9 or 14 columns), one per track() call,
 import optparse
 import sys
 
-from . import longtrack, trackloop
+from . import chiptrack, longtrack, trackloop
 
 
 def _tracker(name):
@@ -56,8 +57,10 @@ def run(name, argv, out=sys.stdout):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     if not argv or argv[0] in ("-h", "--help"):
-        sys.stdout.write(__doc__ + "\ntrackers: " + " ".join(names()) + "\n")
+        sys.stdout.write(__doc__ + "\ntrackers: " + " ".join(names() + sorted(chiptrack.CHIP_TRACKERS)) + "\n")
         return 0
+    if argv[0] in chiptrack.CHIP_TRACKERS:
+        return chiptrack.main(argv)
     run(argv[0], argv[1:])
     return 0
 

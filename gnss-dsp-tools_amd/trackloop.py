@@ -3,8 +3,8 @@
 Every template script runs the same ``track()`` body (track-gps-l1.py:33-94) and the same main loop (:153-179); they differ only in
 the constants of ``TRACKERS``.  ``TrackLoop`` runs K such channels in one launch (csrc/gacq_trackloop.hip, one workgroup per
 channel), each on its own int8 recording resident on the device, and keeps the loop state on the device between calls, so a
-recording can be fed in chunks.  Not template scripts: gps-l2cl and glonass-l1-p/-l2-p run in longtrack; beidou-b2bi/-b2bq
-(nco.accum) are out of scope.
+recording can be fed in chunks.  Not template scripts: gps-l2cl and glonass-l1-p/-l2-p run in longtrack; beidou-b2bi/-b2bq run the
+template loop plus the on-device chip accumulator (nco.accum) in chiptrack.
 """
 import ctypes
 from dataclasses import dataclass
@@ -142,22 +142,34 @@ class TrackLoop:
         self.eng = engine or acquire.default_engine()
         self.channels = list(channels)
         if not self.channels:
-            raise ValueError("TrackLoop needs at least one channel")
-        self.trackers = [TRACKERS[c.name] if c.name in TRACKERS else None for c in self.channels]
-        specs = [channel_spec(c) for c in self.channels]
+            raise ValueError("%s needs at least one channel" % type(self).__name__)
+        self.trackers = [self._trackers().get(c.name) for c in self.channels]
+        specs = [self._channel_spec(c) for c in self.channels]
         self.K = len(specs)
         self._specs = (TrackSpec * self.K)(*specs)
         self.subs_max = max(t.subs for t in self.trackers)
         # a launch covers at most max_records ms of signal per channel, whatever each channel's block length (a record is one
         # track() call, 1 ms in every template script)
         self.max_records = max(int(max_records), self.subs_max)
-        h = ctypes.c_void_p()
-        nat.check(nat.lib.gacq_track_open(self.eng._ctx, self._specs, self.K, ctypes.byref(h)), self.eng._ctx)
-        self._h = h
+        self._h = self._open()
         self._pending = [None] * self.K          # feed(): the unconsumed tail of each channel's samples and its first sample index
         self._base = [0] * self.K
         self.records = [[] for _ in range(self.K)]
         self.status = [0] * self.K
+
+    # what a subclass with its own tracker table and C entry points overrides (chiptrack.ChipTrackLoop)
+    @staticmethod
+    def _trackers():
+        return TRACKERS
+
+    @staticmethod
+    def _channel_spec(ch):
+        return channel_spec(ch)
+
+    def _open(self):
+        h = ctypes.c_void_p()
+        nat.check(nat.lib.gacq_track_open(self.eng._ctx, self._specs, self.K, ctypes.byref(h)), self.eng._ctx)
+        return h
 
     def close(self):
         if self._h:
@@ -174,6 +186,9 @@ class TrackLoop:
         out = np.zeros(1, dtype=STATE_DTYPE)
         nat.check(nat.lib.gacq_track_state(self._h, k, out.ctypes.data_as(ctypes.c_void_p)), self.eng._ctx)
         return out[0]
+
+    def _run_dev(self, ptrs, base, avail, recs, cap, counts, status):
+        return nat.lib.gacq_track_run_dev(self._h, ptrs, base, avail, self.max_records, recs, cap, counts, status)
 
     def _launch(self, xs, bases):
         torch = nat.require_torch()
@@ -198,9 +213,9 @@ class TrackLoop:
         recs = np.zeros((self.K, cap), dtype=RECORD_DTYPE)
         counts = np.zeros(self.K, dtype=np.int32)
         status = np.zeros(self.K, dtype=np.int32)
-        nat.check(nat.lib.gacq_track_run_dev(self._h, ptrs, base.ctypes.data_as(ctypes.c_void_p), avail.ctypes.data_as(ctypes.c_void_p),
-                                             self.max_records, recs.ctypes.data_as(ctypes.c_void_p), cap, counts.ctypes.data_as(nat.c_int_p),
-                                             status.ctypes.data_as(nat.c_int_p)), self.eng._ctx)
+        nat.check(self._run_dev(ptrs, base.ctypes.data_as(ctypes.c_void_p), avail.ctypes.data_as(ctypes.c_void_p),
+                                recs.ctypes.data_as(ctypes.c_void_p), cap, counts.ctypes.data_as(nat.c_int_p),
+                                status.ctypes.data_as(nat.c_int_p)), self.eng._ctx)
         del keep
         out = [recs[k, :counts[k]].copy() for k in range(self.K)]
         for k in range(self.K):

@@ -433,6 +433,24 @@ int gacq_longtrack_run_dev(gacq_longtrack* tr, const void* const* d_x, const lon
 int gacq_longtrack_state(gacq_longtrack* tr, int k, gacq_track_chstate* out);
 void gacq_longtrack_close(gacq_longtrack* tr);
 
+/* ---------------------------------------------------------------------------------------------
+ * Tracking loops with the chip accumulator: track-beidou-b2bi.py / -b2bq.py.  The template loop of gacq_track_* (same specs, records,
+ * states and arithmetic) plus, for every track() call whose frame number (the record's block) exceeds accum_after[k], the script's
+ * nco.accum(+-x, code_p, cf, chips, L): each wiped-off complex64 sample is added to bin floor(code_p + cf*i) mod L of a complex128
+ * accumulator, negated when real(p_prompt) <= 0; every bin is the sequential fp64 sum in sample order, across blocks and launches.
+ * kind 0 and L <= 10240 only.  Accumulator and state persist between gacq_chiptrack_run_dev calls.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gacq_chiptrack gacq_chiptrack;
+
+int gacq_chiptrack_open(gacq_ctx* ctx, const gacq_track_spec* specs, int K, const long long* accum_after, gacq_chiptrack** out);
+/* As gacq_track_run_dev. */
+int gacq_chiptrack_run_dev(gacq_chiptrack* tr, const void* const* d_x, const long long* base, const long long* avail, int max_records,
+                           gacq_track_record* records, int rec_cap, int* counts, int* status);
+int gacq_chiptrack_state(gacq_chiptrack* tr, int k, gacq_track_chstate* out);
+/* Channel k's accumulator: 2 L doubles, re / im interleaved.  Synchronous. */
+int gacq_chiptrack_chips(gacq_chiptrack* tr, int k, double* out);
+void gacq_chiptrack_close(gacq_chiptrack* tr);
+
 /* The loop's two wipe-offs alone, for checking them bit for bit: d_out[k] (complex64) = nco.mix(nco.mix(x, f_offset, p_offset),
  * f_carrier, p_carrier)[k] for the n int8 I/Q samples at d_iq_int8, computed by the loop's own device helpers.  Synchronous. */
 int gacq_track_debug_mix(gacq_ctx* ctx, const void* d_iq_int8, size_t n, double f_offset, double p_offset, double f_carrier,
