@@ -16,6 +16,11 @@ D/N bins per rank); --scaling strong keeps the total work fixed (EPOCHS epochs).
 all-gather of step i is issued asynchronously and merged after step i+1 has been queued.
 
 Prints ONE JSON line (rank 0).  `value` = cells/s of the whole job with inputs resident in HBM.
+
+A plain run does what that line needs and nothing more: set-up, pre-roll, warm-up, the timed steps, --dump-outputs and the line.
+--full adds everything else the benchmark measures or checks: the one-step-in-flight and sustained regions, the shard census, the
+profiling pass and roofline (stream ceilings, live rocprofv3 --pmc traffic), host-call latency, tie-safe counters, the CPU baselines
+and, for the default single-GPU config-2 run, the other BASELINE configurations, the complex128 leg, the next rows and the in-run A/Bs.
 """
 import argparse
 import json
@@ -743,6 +748,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline figure (module docstring); the --no-* switches, "
+                         "--lanes' one-step-in-flight comparison and --sustained-s act on that part.  Without it a run only sets up, "
+                         "warms up, times the steps, writes --dump-outputs and prints the line")
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS), help="BASELINE.json config (2 = the headline metric)")
     ap.add_argument("--epochs", type=int, default=0, help="epochs per GPU per step (default: 1024 / 2 / 2 / 1 for config 2 / 3 / 4 / 5)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
@@ -750,24 +759,24 @@ def main():
     ap.add_argument("--engine", type=int, default=0, help="0 auto, 1 rocFFT pipeline, 2 LDS FFT kernels, 3/4 split engines")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE", help="gacq_set_option tuning switch (e.g. lds_variant=3)")
     ap.add_argument("--distinct-epochs", type=int, default=0, help="N = 4096 signals: distinct seeded epochs per step, tiled to the batch (default: all 1024)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baselines")
     ap.add_argument("--lanes", type=int, default=2,
                     help="steps in flight: engine contexts, each on a HIP stream with a hardware queue of its own, that consecutive "
                          "(independent) steps alternate between.  2 (default): the end of one step -- ragged last round of workgroups, the "
                          "small launches that close a search -- runs under the next step's kernels, and memory-bound and arithmetic-bound "
-                         "searches of a mixed step overlap; the line carries the one-step-in-flight time measured in the same process "
-                         "(roofline.ab.steps_in_flight).  Kernel durations for the roofline come from the profiling pass, which keeps ONE "
+                         "searches of a mixed step overlap; with --full the line carries the one-step-in-flight time measured in the same "
+                         "process (roofline.ab.steps_in_flight).  Kernel durations for the roofline come from the profiling pass, which keeps ONE "
                          "step in flight: overlapped launches have no meaningful duration of their own")
     ap.add_argument("--no-latency", action="store_true",
-                    help="skip the single-epoch host-call latency probe (profiling runs: keeps every launch the bench workload)")
-    ap.add_argument("--sustained-s", type=float, default=1.5, help="length of the second, sustained timed region (0 = skip)")
+                    help="--full: skip the single-epoch host-call latency probe (profiling runs: keeps every launch the bench workload)")
+    ap.add_argument("--sustained-s", type=float, default=1.5, help="--full: length of the second, sustained timed region (0 = skip)")
     ap.add_argument("--preroll-s", type=float, default=0.3, help="untimed load before the warm-up steps so the GPU has clocked up (0 = none)")
     ap.add_argument("--no-self-check", action="store_true", help="variant builds that compute garbage on purpose (tools/build_variant.sh)")
     ap.add_argument("--force-gather", action="store_true", help="run the all-gather + merge even on 1 rank (test aid)")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="skip the live rocprofv3 --pmc child runs that measure the dominant kernel's HBM traffic (N = 1 only; ~15 s each)")
+                    help="--full: skip the live rocprofv3 --pmc child runs that measure the dominant kernel's HBM traffic (N = 1 only; ~15 s each)")
     ap.add_argument("--no-others", action="store_true",
-                    help="headline run only: skip the short runs of configs 3, 4, 5 and the complex128 (engine 5) leg that the default "
+                    help="--full: skip the short runs of configs 3, 4, 5 and the complex128 (engine 5) leg that the full "
                          "single-GPU config-2 run appends as other_configs / reference_precision")
     ap.add_argument("--emulate-ranks", type=int, default=0, metavar="N",
                     help="PROJECTION, not a measurement: on this one GPU, time every rank's slice of an N-rank job (the Doppler slices "
@@ -777,7 +786,7 @@ def main():
                     help="after the timed steps, write what the last timed step returned: every job's merged peak records [epochs, items] "
                          "as float64 DIR/<job>_metric.npy, <job>_code_index.npy, <job>_doppler_index.npy (at most 64 MB in all)")
     ap.add_argument("--details-json", default="", metavar="FILE",
-                    help="also write the complete record to FILE: the printed line cuts the side runs of the default run (other_configs, "
+                    help="also write the complete record to FILE: the printed line cuts the side runs of the --full run (other_configs, "
                          "reference_precision, next_rows) to their headline numbers")
     ap.add_argument("--dry-run-cpu", default="", metavar="FILE.py:FUNCTION",
                     help="NOT A MEASUREMENT: run the N-rank launch path on CPU tensors over gloo with FUNCTION(name, x, items, dopplers, blocks) "
@@ -823,11 +832,12 @@ def main():
 
     t_start = time.perf_counter()
     out = run(args, env)
-    # The default single-GPU headline run also measures the other BASELINE configurations (short runs of the same code path:
+    # The full single-GPU headline run also measures the other BASELINE configurations (short runs of the same code path:
     # >= 1 s timed each, dominant kernel, roofline fraction, HBM traffic measured next to the algorithmic bytes) and the
-    # headline workload in the reference's own arithmetic type (complex128, engine 5), so that the driver-recorded line
+    # headline workload in the reference's own arithmetic type (complex128, engine 5), so that the recorded line
     # carries them.
-    headline = args.config == 2 and world == 1 and args.engine == 0 and not args.no_others and not os.environ.get("GACQ_BENCH_PMC_CHILD")
+    headline = (args.full and args.config == 2 and world == 1 and args.engine == 0 and not args.no_others
+                and not os.environ.get("GACQ_BENCH_PMC_CHILD"))
     if headline and rank == 0:
         others = []
         for k in (3, 4, 5):
@@ -1130,14 +1140,15 @@ def run(args, env):
     run_steps(args.warmup)
     merged, dt = timed(args.steps)
     dumped = host_records(merged) if (args.dump_outputs and rank == 0) else None      # before any later step: the timed path's own output
+    # From here to the record, everything but the self-check (b) is --full only: a plain run goes on to the record, the dump and the teardown.
     one_lane = None
-    if len(lanes) > 1:
+    if args.full and len(lanes) > 1:
         # the same K steps with ONE step in flight (lane 0 only), same process, right after the timed region: what the second step in
         # flight is worth (roofline.ab.steps_in_flight) and the step time the profiling pass's kernel durations belong to
         _, dt_one = make_timed(make_run_steps([((lambda st=lanes[0][0]: torch.cuda.stream(st)), lanes[0][2])], jobs), dev, use_dist)(args.steps)
         one_lane = {"steps_in_flight": 1, "ms_per_step": dt_one / args.steps * 1e3, "value": cells_step * args.steps / dt_one}
     plain_ratio = None
-    if use_dist and world == 1:
+    if args.full and use_dist and world == 1:
         # launched by torch.distributed.run with one rank: the same K steps once more without the barrier / MAX-reduce bracket of the
         # distributed contract -- the two must agree, or the launch path itself costs something
         _, dt_plain = make_timed(run_steps, dev, False)(args.steps)
@@ -1147,7 +1158,7 @@ def run(args, env):
     # the same steps for >= --sustained-s seconds so that DVFS cannot flatter the number (reported beside `value`).
     sustained = None
     clocks = None
-    if args.sustained_s > 0:
+    if args.full and args.sustained_s > 0:
         k_sus, per_step = args.steps, dt / args.steps
         for _ in range(4):                               # the first estimate of the step time may be off: repeat until long enough
             k_sus = max(args.steps, int(np.ceil(1.05 * args.sustained_s / per_step)))
@@ -1168,12 +1179,13 @@ def run(args, env):
             one_lane["sustained"] = {"steps": k_sus, "seconds": dt_one_sus, "ms_per_step": dt_one_sus / k_sus * 1e3, "value": cells_step * k_sus / dt_one_sus}
 
     # ---- correctness of what was just computed (not timed) ----------------------------------------------------------
-    # (a) every rank received `world` shards: one more step with the un-merged exchange buffer kept -- noise alone gives
-    #     every (epoch, item) of every shard a positive metric, so an all-positive shard is one that really arrived
-    shards_seen = 1
-    if exchanged:
+    # (a) --full: every rank received `world` shards: one more step with the un-merged exchange buffer kept -- noise alone gives
+    #     every (epoch, item) of every shard a positive metric, so an all-positive shard is one that really arrived (None: not counted)
+    shards_seen = None if exchanged else 1
+    if args.full and exchanged:
         shards_seen, merged = shard_census(sh, jobs, world, dev)
-    # (b) the strong injected satellites sit at their delays in epoch 0 (padded searches see two code periods: n-d or 2n-d)
+    # (b) the strong injected satellites sit at their delays in epoch 0 (padded searches see two code periods: n-d or 2n-d); it reads
+    #     one epoch of records the timed region already returned, so plain runs keep it: a build that computes garbage prints no figure
     if not args.no_self_check:
         for job, m in zip(jobs, merged):
             pk = m[:1].cpu().numpy().view(acquire.PEAK_DTYPE).reshape(job["P"])
@@ -1183,198 +1195,200 @@ def run(args, env):
                     got = int(pk["idx"][job["flat"].index(it)])
                     assert got % n == (-delay) % n, ("bench self-check failed", job["sig"].name, it, got, delay)
 
-    # ---- per-kernel durations: HIP events on the launch stream, in a pass that reproduces the timed region ------------------------
-    # Stage timers are per engine context, so every job gets its own profiling engine (same stream, same options, same call path) and
-    # the pass runs whole steps -- all jobs back to back, pipelined like run_steps(), for >= 0.5 s -- so that the kernels are timed
-    # in the thermal / clock state of the timed region and next to the same neighbours.  (Round 2 timed one job at a time in a short
-    # loop: for the four-signal config 5 that read 11 % faster than the rocprofv3 trace of the timed region.)
-    bounds_of = lambda D: sharded.doppler_bounds(D, world)
-    st0, eng0, sh0 = lanes[0]
-    prof_steps = max(3, min(10, args.steps), int(np.ceil(0.5 / max(dt / args.steps, 1e-6))))
-    if use_dist:
-        kt = torch.tensor([prof_steps], dtype=torch.int64, device=dev)
-        dist.all_reduce(kt, op=dist.ReduceOp.MAX)
-        prof_steps = int(kt.item())
-    if len(jobs) == 1:
-        prof = [(eng0, sh0)]
-    else:
-        prof = []
+    roofline = per_job = None
+    if args.full:
+        # ---- per-kernel durations: HIP events on the launch stream, in a pass that reproduces the timed region ------------------------
+        # Stage timers are per engine context, so every job gets its own profiling engine (same stream, same options, same call path) and
+        # the pass runs whole steps -- all jobs back to back, pipelined like run_steps(), for >= 0.5 s -- so that the kernels are timed
+        # in the thermal / clock state of the timed region and next to the same neighbours.  (Round 2 timed one job at a time in a short
+        # loop: for the four-signal config 5 that read 11 % faster than the rocprofv3 trace of the timed region.)
+        bounds_of = lambda D: sharded.doppler_bounds(D, world)
+        st0, eng0, sh0 = lanes[0]
+        prof_steps = max(3, min(10, args.steps), int(np.ceil(0.5 / max(dt / args.steps, 1e-6))))
+        if use_dist:
+            kt = torch.tensor([prof_steps], dtype=torch.int64, device=dev)
+            dist.all_reduce(kt, op=dist.ReduceOp.MAX)
+            prof_steps = int(kt.item())
+        if len(jobs) == 1:
+            prof = [(eng0, sh0)]
+        else:
+            prof = []
+            with torch.cuda.stream(st0):
+                for _ in jobs:
+                    ej = make_engine()
+                    prof.append((ej, sharded.ShardedSearch(engine=ej, always_gather=args.force_gather)))
         with torch.cuda.stream(st0):
-            for _ in jobs:
-                ej = make_engine()
-                prof.append((ej, sharded.ShardedSearch(engine=ej, always_gather=args.force_gather)))
-    with torch.cuda.stream(st0):
-        for (ej, shj), job in zip(prof, jobs):
-            shj.search_jobs_async([job]).wait()          # settle (signal build, grid upload) before the events start
+            for (ej, shj), job in zip(prof, jobs):
+                shj.search_jobs_async([job]).wait()          # settle (signal build, grid upload) before the events start
+            torch.cuda.synchronize(dev)
+            for ej, _ in prof:
+                ej.set_profiling(True)
+                ej.reset_stage_times()
+            pend = [None] * len(jobs)
+            t_prof = time.perf_counter()
+            for _ in range(prof_steps):
+                for ji, ((ej, shj), job) in enumerate(zip(prof, jobs)):
+                    nxt = shj.search_jobs_async([job])
+                    if pend[ji] is not None:
+                        pend[ji].wait()
+                    pend[ji] = nxt
+            for pj_ in pend:
+                pj_.wait()
         torch.cuda.synchronize(dev)
-        for ej, _ in prof:
-            ej.set_profiling(True)
-            ej.reset_stage_times()
-        pend = [None] * len(jobs)
-        t_prof = time.perf_counter()
-        for _ in range(prof_steps):
-            for ji, ((ej, shj), job) in enumerate(zip(prof, jobs)):
-                nxt = shj.search_jobs_async([job])
-                if pend[ji] is not None:
-                    pend[ji].wait()
-                pend[ji] = nxt
-        for pj_ in pend:
-            pj_.wait()
-    torch.cuda.synchronize(dev)
-    prof_ms_per_step = (time.perf_counter() - t_prof) / prof_steps * 1e3
-    per_job = []
-    for (ej, _), job in zip(prof, jobs):
-        b = bounds_of(len(job["dop"]))
-        D_local = b[rank + 1] - b[rank]
-        stages = ej.stage_times()
-        ej.set_profiling(False)
-        N, P, B, F = job["sig"].nfft, job["P"], job["B"], job["F"]
-        fused16k = job["kind"] == "lds" and N == 16384 and F == P
-        fused4k = job["kind"] == "lds" and N == 4096 and not stages["mix_nco"][1] and stages["lds_correlate"][1] > 0
-        st_out = {}
-        for sname, (tot_ms, nl) in stages.items():
-            if not nl:
-                continue
-            bound, work = stage_model(job["kind"], sname, N, P, D_local, B, F, E_total, fused16k, fused4k)
-            st_out[sname] = {"avg_ms": tot_ms / nl, "launches_per_step": nl / prof_steps, "ms_per_step": tot_ms / prof_steps,
-                             "bound": bound, "work_per_step": work}
-        per_job.append({"signal": job["label"], "engine": job["kind"], "P": P, "D_local": D_local, "B": B, "N": N, "F": F, "stages": st_out,
-                        "fused_forward": bool(fused16k or fused4k)})
-    if len(jobs) > 1:
-        for ej, _ in prof:
-            ej.close()
+        prof_ms_per_step = (time.perf_counter() - t_prof) / prof_steps * 1e3
+        per_job = []
+        for (ej, _), job in zip(prof, jobs):
+            b = bounds_of(len(job["dop"]))
+            D_local = b[rank + 1] - b[rank]
+            stages = ej.stage_times()
+            ej.set_profiling(False)
+            N, P, B, F = job["sig"].nfft, job["P"], job["B"], job["F"]
+            fused16k = job["kind"] == "lds" and N == 16384 and F == P
+            fused4k = job["kind"] == "lds" and N == 4096 and not stages["mix_nco"][1] and stages["lds_correlate"][1] > 0
+            st_out = {}
+            for sname, (tot_ms, nl) in stages.items():
+                if not nl:
+                    continue
+                bound, work = stage_model(job["kind"], sname, N, P, D_local, B, F, E_total, fused16k, fused4k)
+                st_out[sname] = {"avg_ms": tot_ms / nl, "launches_per_step": nl / prof_steps, "ms_per_step": tot_ms / prof_steps,
+                                 "bound": bound, "work_per_step": work}
+            per_job.append({"signal": job["label"], "engine": job["kind"], "P": P, "D_local": D_local, "B": B, "N": N, "F": F, "stages": st_out,
+                            "fused_forward": bool(fused16k or fused4k)})
+        if len(jobs) > 1:
+            for ej, _ in prof:
+                ej.close()
 
-    # dominant kernel = the (signal, stage) with the most time per step
-    cand = [(s["ms_per_step"], pj, sname) for pj in per_job for sname, s in pj["stages"].items() if s["bound"]]
-    _, dj, dstage = max(cand, key=lambda c: c[0])
-    dk = dj["stages"][dstage]
-    work_launch = dk["work_per_step"] / dk["launches_per_step"]
-    kernel_name = {("lds", "lds_correlate", 4096): "lds_correlate_kernel", ("lds", "lds_correlate", 16384): "r32_correlate_kernel / r32_fused_kernel",
-                   ("lds", "mix_nco", 4096): "lds_forward_kernel", ("lds", "mix_nco", 16384): "r32_forward_kernel",
-                   ("split31", "lds_correlate"): "pfa_inner_corr_kernel", ("split_lds", "lds_correlate"): "lds_inner_correlate_kernel",
-                   ("split31", "mag_peak"): "pfa_outer_inverse_kernel", ("split_lds", "mag_peak"): "split_outer_inverse_kernel",
-                   ("split31", "mix_nco"): "pfa_outer_forward_kernel + pfa_inner_forward_kernel", ("split_lds", "mix_nco"): "split_outer_forward_kernel + lds_inner_forward_kernel"}
-    kname = kernel_name.get((dj["engine"], dstage, dj["N"])) or kernel_name.get((dj["engine"], dstage)) or dstage
-    if dj["engine"] == "lds" and dstage == "lds_correlate":
-        kname = {(4096, True): "lds_fused4k_kernel", (4096, False): "lds_correlate_kernel", (16384, True): "lds16k_fused_kernel",
-                 (16384, False): "lds16k_correlate_kernel"}[(dj["N"], dj["fused_forward"])]
-        if dj["N"] == 16384 and "lds_variant=16" not in args.option:
-            kname = "r32_fused_kernel" if dj["fused_forward"] else "r32_correlate_kernel"
-    if dk["bound"] == "valu":
-        achieved = work_launch / (dk["avg_ms"] * 1e-3) / 1e12
-        roofline = {"bound": "valu", "kernel": kname, "signal": dj["signal"], "achieved": achieved, "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": achieved / VALU_PEAK_TFLOPS, "avg_kernel_ms": dk["avg_ms"], "useful_flop_per_launch": work_launch,
-                    "model": "useful FP32 flop of the rows one launch transforms (5 N log2 N per FFT + 6 N per complex product + 4 N for |.|) "
-                             "over the kernel's HIP-event duration, against the FP32 vector peak; the kernel keeps every stage boundary in "
-                             "LDS/registers, so HBM is not what bounds it (see traffic and pipeline_equivalent)"}
-    else:
-        achieved = work_launch / (dk["avg_ms"] * 1e-3) / 1e9
-        roofline = {"bound": "hbm", "kernel": kname, "signal": dj["signal"], "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                    "frac": achieved / HBM_PEAK_GBPS, "avg_kernel_ms": dk["avg_ms"], "alg_bytes_per_launch": work_launch,
-                    "model": "bytes this kernel must move through HBM: its side of the split engine's one round trip (8 N per correlation "
-                             "row), or x in + X out for the forward stage, over the kernel's HIP-event duration"}
-    # The kernel's HIP-event time comes from the profiling pass (one engine per job, events around every stage), `ms_per_step` from the
-    # timed region: two loops, so the pass carries its own wall-clock step time -- the kernel time of a step can only be read against
-    # THAT -- and the line also prices the dominant kernel against the timed region's step time, a bound that needs no second loop.
-    k_ms_step = dk["avg_ms"] * dk["launches_per_step"]
-    roofline["profiling_pass"] = {"steps": prof_steps, "ms_per_step": prof_ms_per_step, "dominant_kernel_ms_per_step": k_ms_step,
-                                  "kernel_time_within_its_own_step": bool(k_ms_step <= prof_ms_per_step * 1.0005)}
-    roofline["frac_floor_from_timed_step"] = roofline["frac"] * k_ms_step / max(k_ms_step, dt / args.steps * 1e3)
-    if clocks and clocks.get("sclk_mhz_mean"):
-        roofline["clocks"] = clocks
-        if dk["bound"] == "valu":      # the FP32 vector peak is 256 CUs x 4 SIMDs x 32 lanes x 2 (packed) x 2 flop x 2.4 GHz
-            roofline["frac_at_measured_clock"] = roofline["frac"] * 2400.0 / clocks["sclk_mhz_mean"]
-    if dk["bound"] == "hbm":
-        # `peak` stays the 8 TB/s of MI355X_MICROARCH.md; what a plain streaming kernel reaches on this part is lower and differs by
-        # direction (tools/hbm_bandwidth.hip, profiles/r03_hbm_read_write_copy_bandwidth.log): 16-byte stores 4.2-4.7 TB/s, loads 6.5-7.1
-        # measured in this run on this device by a tuned streaming kernel (gacq_stream_probe), not constants from an earlier box
-        kind = "read" if dstage == "mag_peak" else ("fill" if dstage == "lds_correlate" else "copy")
-        try:
-            ceil = stream_ceilings(eng0)
-            sc = {"side": kind, "GBps": ceil[kind], "all": ceil, "measured_in_this_run": True,
-                  "source": "gacq_stream_probe: 8 x 16-byte non-temporal accesses in flight per lane, 1 GiB per launch, 8 timed launches"}
-            if roofline["achieved"] <= ceil[kind]:
-                sc["frac"] = roofline["achieved"] / ceil[kind]
-            else:            # a kernel faster than the probe: the probe is then no ceiling for it, and no fraction > 1 is printed
-                sc["exceeded_by_kernel"] = True
-            roofline["stream_ceiling"] = sc
-        except Exception as exc:
-            roofline["stream_ceiling"] = {"error": repr(exc)[:200]}
-    # what the dominant kernel must at least move through HBM per launch (inputs once, outputs once): the yardstick for `traffic`
-    # The PMC passes below average over EVERY launch of that kernel in a step, so the yardstick does too: jobs of the step that run the
-    # same kernel on the same FFT length (config 4: L5I and B2aD) are pooled, compulsory bytes per step over launches per step.
-    def compulsory_step(pj):
-        job_ = next(j for j in jobs if j["label"] == pj["signal"])
-        k_ = pj["stages"][dstage]
-        rec_ = 16.0 * E_total * pj["P"] * pj["D_local"]
-        spectra_ = float(S * pj["P"] * pj["N"])
-        x_rows_ = float(S) * E_total * pj["F"] * pj["D_local"] * pj["B"] * pj["N"]       # forward spectra [E][F][D][B][N]
-        x_samples_ = float(S) * E_total * job_["xs"].shape[1]
-        if k_["bound"] == "hbm":
-            return k_["work_per_step"] + ((x_rows_ + spectra_) if dstage == "lds_correlate" else (rec_ if dstage == "mag_peak" else 0.0))
-        return (x_samples_ if pj["fused_forward"] else x_rows_) + spectra_ + rec_
-    pool = [pj for pj in per_job if pj["engine"] == dj["engine"] and pj["N"] == dj["N"] and dstage in pj["stages"]
-            and pj["fused_forward"] == dj["fused_forward"]]
-    roofline["compulsory_bytes_per_launch"] = sum(compulsory_step(pj) for pj in pool) / sum(pj["stages"][dstage]["launches_per_step"] for pj in pool)
-    if len(pool) > 1:
-        roofline["compulsory_pooled_over"] = [pj["signal"] for pj in pool]
-    # Measured HBM traffic of the dominant kernel: rocprofv3 --pmc wraps a command, so rank 0 of a single-GPU run re-runs this
-    # very command line (3 steps, no baselines) under it, one counter group per child run, and reads the kernel's FETCH_SIZE /
-    # WRITE_SIZE (KiB; FETCH_SIZE doubled: on gfx950 it counts half of a wide coalesced read -- MI355X_MICROARCH.md, HBM
-    # section).  If that cannot be done here (no rocprofv3, child failed) the committed PMC summary of the same command under
-    # profiles/ is replayed instead and labelled as such; it is dropped when it describes another kernel, batch or world size.
-    roofline["traffic"] = None
-    under_profiler = any(k.startswith(("ROCPROF", "ROCP_TOOL")) for k in os.environ)       # never nest profilers
-    if world == 1 and rank == 0 and not args.no_pmc and not under_profiler and not os.environ.get("GACQ_BENCH_PMC_CHILD"):
-        child = ["--gpus", "1", "--config", str(args.config), "--epochs", str(epochs), "--steps", "3", "--warmup", "1", "--engine", str(args.engine),
-                 "--no-cpu-baseline", "--no-latency", "--sustained-s", "0", "--preroll-s", "0", "--no-pmc", "--no-others", "--lanes", "1"]
-        for kv in args.option:
-            child += ["--option", kv]
-        if args.no_self_check:
-            child.append("--no-self-check")
-        passes = [["FETCH_SIZE"], ["WRITE_SIZE"]]
+        # dominant kernel = the (signal, stage) with the most time per step
+        cand = [(s["ms_per_step"], pj, sname) for pj in per_job for sname, s in pj["stages"].items() if s["bound"]]
+        _, dj, dstage = max(cand, key=lambda c: c[0])
+        dk = dj["stages"][dstage]
+        work_launch = dk["work_per_step"] / dk["launches_per_step"]
+        kernel_name = {("lds", "lds_correlate", 4096): "lds_correlate_kernel", ("lds", "lds_correlate", 16384): "r32_correlate_kernel / r32_fused_kernel",
+                       ("lds", "mix_nco", 4096): "lds_forward_kernel", ("lds", "mix_nco", 16384): "r32_forward_kernel",
+                       ("split31", "lds_correlate"): "pfa_inner_corr_kernel", ("split_lds", "lds_correlate"): "lds_inner_correlate_kernel",
+                       ("split31", "mag_peak"): "pfa_outer_inverse_kernel", ("split_lds", "mag_peak"): "split_outer_inverse_kernel",
+                       ("split31", "mix_nco"): "pfa_outer_forward_kernel + pfa_inner_forward_kernel", ("split_lds", "mix_nco"): "split_outer_forward_kernel + lds_inner_forward_kernel"}
+        kname = kernel_name.get((dj["engine"], dstage, dj["N"])) or kernel_name.get((dj["engine"], dstage)) or dstage
+        if dj["engine"] == "lds" and dstage == "lds_correlate":
+            kname = {(4096, True): "lds_fused4k_kernel", (4096, False): "lds_correlate_kernel", (16384, True): "lds16k_fused_kernel",
+                     (16384, False): "lds16k_correlate_kernel"}[(dj["N"], dj["fused_forward"])]
+            if dj["N"] == 16384 and "lds_variant=16" not in args.option:
+                kname = "r32_fused_kernel" if dj["fused_forward"] else "r32_correlate_kernel"
         if dk["bound"] == "valu":
-            passes.append(["GRBM_GUI_ACTIVE", "SQ_ACTIVE_INST_VALU"])
-        t_pmc = time.perf_counter()
-        try:
-            pm = pmc_passes(child, kname.split("<")[0].split(" ")[0], passes)
-            roofline["traffic"] = (2.0 * pm["FETCH_SIZE"] + pm["WRITE_SIZE"]) * 1024.0
-            roofline["traffic_source"] = {"measured_in_this_run": True, "method": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE child runs of this "
-                                          "command (separate passes), bytes = (2 x FETCH_SIZE + WRITE_SIZE) x 1024 per launch",
-                                          "fetch_size_kib_raw": pm["FETCH_SIZE"], "write_size_kib": pm["WRITE_SIZE"], "launches_averaged": pm["launches"],
-                                          "seconds": None}
-            if "SQ_ACTIVE_INST_VALU" in pm and pm.get("GRBM_GUI_ACTIVE"):
-                # GRBM_GUI_ACTIVE sums the 8 XCDs; SQ_ACTIVE_INST_VALU counts quad-cycles over 1024 SIMDs (tools/pmc_profile.py)
-                roofline["traffic_source"]["valu_pipe_busy_pmc"] = 4.0 * pm["SQ_ACTIVE_INST_VALU"] / (pm["GRBM_GUI_ACTIVE"] / 8.0 * 1024.0)
-            roofline["traffic_source"]["seconds"] = time.perf_counter() - t_pmc
-        except Exception as exc:
-            roofline["traffic_source"] = {"measured_in_this_run": False, "live_error": repr(exc)[:300]}
-    tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-    if roofline["traffic"] is None and os.path.exists(tpath) and world == 1:
-        try:
-            tj = json.load(open(tpath))
-            if tj.get("config", 2) == args.config and tj.get("kernel_stage") == dstage and tj.get("epochs") == E_total:
-                roofline["traffic"] = tj.get("hbm_bytes_per_launch")
-                src = roofline.get("traffic_source") or {}
-                src.update({"measured_in_this_run": False, "file": "profiles/traffic_latest.json",
-                            "from": tj.get("source"), "valu_pipe_busy_pmc": tj.get("valu_pipe_busy")})
-                roofline["traffic_source"] = src
-        except Exception:
-            pass
-    # the SURVEY 8d stage-boundary figure, kept as a secondary number: how a perfect HBM-bound five-stage pipeline would
-    # have to perform to match the measured step (it exceeds the HBM peak for the fused engines, i.e. it is not a fraction)
-    a_pipe_step = sum(a_pipe_bytes(j["sig"].nfft, j["P"], len(j["dop"]), j["B"], j["F"]) for j in jobs) * E_total
-    roofline["pipeline_equivalent"] = {"a_pipe_bytes_per_step": a_pipe_step, "GBps": a_pipe_step / (dt / args.steps) / 1e9,
-                                       "times_hbm_peak": a_pipe_step / (dt / args.steps) / 1e9 / HBM_PEAK_GBPS}
-    if use_dist:
-        mine = torch.tensor([roofline["frac"], dk["avg_ms"]], dtype=torch.float64, device=dev)
-        allr = torch.empty(world * 2, dtype=torch.float64, device=dev)
-        dist.all_gather_into_tensor(allr, mine)
-        roofline["per_rank"] = [{"rank": r, "frac": float(allr[2 * r]), "avg_kernel_ms": float(allr[2 * r + 1])} for r in range(world)]
+            achieved = work_launch / (dk["avg_ms"] * 1e-3) / 1e12
+            roofline = {"bound": "valu", "kernel": kname, "signal": dj["signal"], "achieved": achieved, "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": achieved / VALU_PEAK_TFLOPS, "avg_kernel_ms": dk["avg_ms"], "useful_flop_per_launch": work_launch,
+                        "model": "useful FP32 flop of the rows one launch transforms (5 N log2 N per FFT + 6 N per complex product + 4 N for |.|) "
+                                 "over the kernel's HIP-event duration, against the FP32 vector peak; the kernel keeps every stage boundary in "
+                                 "LDS/registers, so HBM is not what bounds it (see traffic and pipeline_equivalent)"}
+        else:
+            achieved = work_launch / (dk["avg_ms"] * 1e-3) / 1e9
+            roofline = {"bound": "hbm", "kernel": kname, "signal": dj["signal"], "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBPS, "avg_kernel_ms": dk["avg_ms"], "alg_bytes_per_launch": work_launch,
+                        "model": "bytes this kernel must move through HBM: its side of the split engine's one round trip (8 N per correlation "
+                                 "row), or x in + X out for the forward stage, over the kernel's HIP-event duration"}
+        # The kernel's HIP-event time comes from the profiling pass (one engine per job, events around every stage), `ms_per_step` from the
+        # timed region: two loops, so the pass carries its own wall-clock step time -- the kernel time of a step can only be read against
+        # THAT -- and the line also prices the dominant kernel against the timed region's step time, a bound that needs no second loop.
+        k_ms_step = dk["avg_ms"] * dk["launches_per_step"]
+        roofline["profiling_pass"] = {"steps": prof_steps, "ms_per_step": prof_ms_per_step, "dominant_kernel_ms_per_step": k_ms_step,
+                                      "kernel_time_within_its_own_step": bool(k_ms_step <= prof_ms_per_step * 1.0005)}
+        roofline["frac_floor_from_timed_step"] = roofline["frac"] * k_ms_step / max(k_ms_step, dt / args.steps * 1e3)
+        if clocks and clocks.get("sclk_mhz_mean"):
+            roofline["clocks"] = clocks
+            if dk["bound"] == "valu":      # the FP32 vector peak is 256 CUs x 4 SIMDs x 32 lanes x 2 (packed) x 2 flop x 2.4 GHz
+                roofline["frac_at_measured_clock"] = roofline["frac"] * 2400.0 / clocks["sclk_mhz_mean"]
+        if dk["bound"] == "hbm":
+            # `peak` stays the 8 TB/s of MI355X_MICROARCH.md; what a plain streaming kernel reaches on this part is lower and differs by
+            # direction (tools/hbm_bandwidth.hip, profiles/r03_hbm_read_write_copy_bandwidth.log): 16-byte stores 4.2-4.7 TB/s, loads 6.5-7.1
+            # measured in this run on this device by a tuned streaming kernel (gacq_stream_probe), not constants from an earlier box
+            kind = "read" if dstage == "mag_peak" else ("fill" if dstage == "lds_correlate" else "copy")
+            try:
+                ceil = stream_ceilings(eng0)
+                sc = {"side": kind, "GBps": ceil[kind], "all": ceil, "measured_in_this_run": True,
+                      "source": "gacq_stream_probe: 8 x 16-byte non-temporal accesses in flight per lane, 1 GiB per launch, 8 timed launches"}
+                if roofline["achieved"] <= ceil[kind]:
+                    sc["frac"] = roofline["achieved"] / ceil[kind]
+                else:            # a kernel faster than the probe: the probe is then no ceiling for it, and no fraction > 1 is printed
+                    sc["exceeded_by_kernel"] = True
+                roofline["stream_ceiling"] = sc
+            except Exception as exc:
+                roofline["stream_ceiling"] = {"error": repr(exc)[:200]}
+        # what the dominant kernel must at least move through HBM per launch (inputs once, outputs once): the yardstick for `traffic`
+        # The PMC passes below average over EVERY launch of that kernel in a step, so the yardstick does too: jobs of the step that run the
+        # same kernel on the same FFT length (config 4: L5I and B2aD) are pooled, compulsory bytes per step over launches per step.
+        def compulsory_step(pj):
+            job_ = next(j for j in jobs if j["label"] == pj["signal"])
+            k_ = pj["stages"][dstage]
+            rec_ = 16.0 * E_total * pj["P"] * pj["D_local"]
+            spectra_ = float(S * pj["P"] * pj["N"])
+            x_rows_ = float(S) * E_total * pj["F"] * pj["D_local"] * pj["B"] * pj["N"]       # forward spectra [E][F][D][B][N]
+            x_samples_ = float(S) * E_total * job_["xs"].shape[1]
+            if k_["bound"] == "hbm":
+                return k_["work_per_step"] + ((x_rows_ + spectra_) if dstage == "lds_correlate" else (rec_ if dstage == "mag_peak" else 0.0))
+            return (x_samples_ if pj["fused_forward"] else x_rows_) + spectra_ + rec_
+        pool = [pj for pj in per_job if pj["engine"] == dj["engine"] and pj["N"] == dj["N"] and dstage in pj["stages"]
+                and pj["fused_forward"] == dj["fused_forward"]]
+        roofline["compulsory_bytes_per_launch"] = sum(compulsory_step(pj) for pj in pool) / sum(pj["stages"][dstage]["launches_per_step"] for pj in pool)
+        if len(pool) > 1:
+            roofline["compulsory_pooled_over"] = [pj["signal"] for pj in pool]
+        # Measured HBM traffic of the dominant kernel: rocprofv3 --pmc wraps a command, so rank 0 of a single-GPU run re-runs this
+        # very command line (3 steps, no baselines) under it, one counter group per child run, and reads the kernel's FETCH_SIZE /
+        # WRITE_SIZE (KiB; FETCH_SIZE doubled: on gfx950 it counts half of a wide coalesced read -- MI355X_MICROARCH.md, HBM
+        # section).  If that cannot be done here (no rocprofv3, child failed) the committed PMC summary of the same command under
+        # profiles/ is replayed instead and labelled as such; it is dropped when it describes another kernel, batch or world size.
+        roofline["traffic"] = None
+        under_profiler = any(k.startswith(("ROCPROF", "ROCP_TOOL")) for k in os.environ)       # never nest profilers
+        if world == 1 and rank == 0 and not args.no_pmc and not under_profiler and not os.environ.get("GACQ_BENCH_PMC_CHILD"):
+            child = ["--gpus", "1", "--config", str(args.config), "--epochs", str(epochs), "--steps", "3", "--warmup", "1", "--engine", str(args.engine),
+                     "--no-cpu-baseline", "--no-latency", "--sustained-s", "0", "--preroll-s", "0", "--no-pmc", "--no-others", "--lanes", "1", "--full"]
+            for kv in args.option:
+                child += ["--option", kv]
+            if args.no_self_check:
+                child.append("--no-self-check")
+            passes = [["FETCH_SIZE"], ["WRITE_SIZE"]]
+            if dk["bound"] == "valu":
+                passes.append(["GRBM_GUI_ACTIVE", "SQ_ACTIVE_INST_VALU"])
+            t_pmc = time.perf_counter()
+            try:
+                pm = pmc_passes(child, kname.split("<")[0].split(" ")[0], passes)
+                roofline["traffic"] = (2.0 * pm["FETCH_SIZE"] + pm["WRITE_SIZE"]) * 1024.0
+                roofline["traffic_source"] = {"measured_in_this_run": True, "method": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE child runs of this "
+                                              "command (separate passes), bytes = (2 x FETCH_SIZE + WRITE_SIZE) x 1024 per launch",
+                                              "fetch_size_kib_raw": pm["FETCH_SIZE"], "write_size_kib": pm["WRITE_SIZE"], "launches_averaged": pm["launches"],
+                                              "seconds": None}
+                if "SQ_ACTIVE_INST_VALU" in pm and pm.get("GRBM_GUI_ACTIVE"):
+                    # GRBM_GUI_ACTIVE sums the 8 XCDs; SQ_ACTIVE_INST_VALU counts quad-cycles over 1024 SIMDs (tools/pmc_profile.py)
+                    roofline["traffic_source"]["valu_pipe_busy_pmc"] = 4.0 * pm["SQ_ACTIVE_INST_VALU"] / (pm["GRBM_GUI_ACTIVE"] / 8.0 * 1024.0)
+                roofline["traffic_source"]["seconds"] = time.perf_counter() - t_pmc
+            except Exception as exc:
+                roofline["traffic_source"] = {"measured_in_this_run": False, "live_error": repr(exc)[:300]}
+        tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+        if roofline["traffic"] is None and os.path.exists(tpath) and world == 1:
+            try:
+                tj = json.load(open(tpath))
+                if tj.get("config", 2) == args.config and tj.get("kernel_stage") == dstage and tj.get("epochs") == E_total:
+                    roofline["traffic"] = tj.get("hbm_bytes_per_launch")
+                    src = roofline.get("traffic_source") or {}
+                    src.update({"measured_in_this_run": False, "file": "profiles/traffic_latest.json",
+                                "from": tj.get("source"), "valu_pipe_busy_pmc": tj.get("valu_pipe_busy")})
+                    roofline["traffic_source"] = src
+            except Exception:
+                pass
+        # the SURVEY 8d stage-boundary figure, kept as a secondary number: how a perfect HBM-bound five-stage pipeline would
+        # have to perform to match the measured step (it exceeds the HBM peak for the fused engines, i.e. it is not a fraction)
+        a_pipe_step = sum(a_pipe_bytes(j["sig"].nfft, j["P"], len(j["dop"]), j["B"], j["F"]) for j in jobs) * E_total
+        roofline["pipeline_equivalent"] = {"a_pipe_bytes_per_step": a_pipe_step, "GBps": a_pipe_step / (dt / args.steps) / 1e9,
+                                           "times_hbm_peak": a_pipe_step / (dt / args.steps) / 1e9 / HBM_PEAK_GBPS}
+        if use_dist:
+            mine = torch.tensor([roofline["frac"], dk["avg_ms"]], dtype=torch.float64, device=dev)
+            allr = torch.empty(world * 2, dtype=torch.float64, device=dev)
+            dist.all_gather_into_tensor(allr, mine)
+            roofline["per_rank"] = [{"rank": r, "frac": float(allr[2 * r]), "avg_kernel_ms": float(allr[2 * r + 1])} for r in range(world)]
 
     # host-buffer entry points (H2D + launches + D2H + sync): the drop-in search() call surface; not part of `value`
     latency = None
-    if world == 1 and not args.no_latency and args.config == 2:
+    if args.full and world == 1 and not args.no_latency and args.config == 2:
         job = jobs[0]
         sig, items, ds, ms, dop, B = job["sig"], job["items"], job["ds"], job["ms"], job["dop"], job["B"]
         P, D, N = len(items), len(dop), sig.nfft
@@ -1466,36 +1480,37 @@ def run(args, env):
             out["config"]["collective_backend"] = dist.get_backend()
             out["config"]["ranks_in_the_process_group"] = dist.get_world_size()
             assert dist.get_world_size() == world and (args.gpus == world or world == 1), ("launched with --gpus %d, the process group has %d ranks" % (args.gpus, dist.get_world_size()))
-        # tie-safe peak locations run inside every timed step (tagging in the row reductions, the ambiguity test in the Doppler scan, the
-        # re-evaluation launches); the counters say how many pairs of this run needed the complex128 re-evaluation -- the bench's
-        # epochs carry strong injected satellites, so usually none (tools/tie_census.py is the noise-only census)
-        try:
-            eng_t = lanes[0][1]
-            before = eng_t.tie_stats()
-            run_steps(1)                                           # one more (untimed) step on lane 0: the counters of exactly one step
-            torch.cuda.synchronize(dev)
-            after = eng_t.tie_stats()
-            out["tie_safe"] = dict(after, enabled=bool(eng_t.get_option("tie_safe")), eps=eng_t.get_option("tie_eps_ppb") * 1e-9,
-                                   distinct_epochs_per_step=int(sum(len(j["host"]) for j in jobs)),
-                                   per_step={k: after[k] - before[k] for k in before})
-            if after["kept_fp32"]:
-                out["tie_safe"]["warning"] = ("%d ambiguous pairs kept their fp32 answer (re-evaluation list full or unsupported length): raise "
-                                              "GACQ_OPT_TIE_CAP" % after["kept_fp32"])
-            if out["tie_safe"]["enabled"] and world == 1:
-                # what the tie-safe machinery costs: the same steps with it switched off, same process, right after the timed region
-                for _, e_l, _ in lanes:
-                    e_l.set_option("tie_safe", 0)
-                try:
-                    _, dt_off = timed(args.steps)
-                finally:
+        if args.full:
+            # tie-safe peak locations run inside every timed step (tagging in the row reductions, the ambiguity test in the Doppler scan, the
+            # re-evaluation launches); the counters say how many pairs of this run needed the complex128 re-evaluation -- the bench's
+            # epochs carry strong injected satellites, so usually none (tools/tie_census.py is the noise-only census)
+            try:
+                eng_t = lanes[0][1]
+                before = eng_t.tie_stats()
+                run_steps(1)                                           # one more (untimed) step on lane 0: the counters of exactly one step
+                torch.cuda.synchronize(dev)
+                after = eng_t.tie_stats()
+                out["tie_safe"] = dict(after, enabled=bool(eng_t.get_option("tie_safe")), eps=eng_t.get_option("tie_eps_ppb") * 1e-9,
+                                       distinct_epochs_per_step=int(sum(len(j["host"]) for j in jobs)),
+                                       per_step={k: after[k] - before[k] for k in before})
+                if after["kept_fp32"]:
+                    out["tie_safe"]["warning"] = ("%d ambiguous pairs kept their fp32 answer (re-evaluation list full or unsupported length): raise "
+                                                  "GACQ_OPT_TIE_CAP" % after["kept_fp32"])
+                if out["tie_safe"]["enabled"] and world == 1:
+                    # what the tie-safe machinery costs: the same steps with it switched off, same process, right after the timed region
                     for _, e_l, _ in lanes:
-                        e_l.set_option("tie_safe", 1)
-                out["tie_safe"]["ms_per_step_with_tie_safe_off"] = dt_off / args.steps * 1e3
-        except Exception as exc:
-            out["tie_safe"] = {"error": repr(exc)[:200]}
-        if args.config == 2:            # keep the flat stage table of the single-signal line (profiles/)
+                        e_l.set_option("tie_safe", 0)
+                    try:
+                        _, dt_off = timed(args.steps)
+                    finally:
+                        for _, e_l, _ in lanes:
+                            e_l.set_option("tie_safe", 1)
+                    out["tie_safe"]["ms_per_step_with_tie_safe_off"] = dt_off / args.steps * 1e3
+            except Exception as exc:
+                out["tie_safe"] = {"error": repr(exc)[:200]}
+        if args.config == 2 and per_job:     # keep the flat stage table of the single-signal line (profiles/)
             out["pipeline"]["stages"] = per_job[0]["stages"]
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(jobs)
             out["cpu_baseline"]["host"] = host_info()
             out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]

@@ -516,7 +516,7 @@ def test_bench_under_torchrun_single_rank_exercises_rccl_path(config, extra):
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--config", str(config), "--force-gather", "--no-cpu-baseline", "--no-pmc", "--sustained-s", "0.2"] + extra
+           "--config", str(config), "--force-gather", "--full", "--no-cpu-baseline", "--no-pmc", "--sustained-s", "0.2"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -529,7 +529,7 @@ def test_bench_under_torchrun_single_rank_exercises_rccl_path(config, extra):
 
 def test_bench_torchrun_single_rank_value_equals_the_plain_run():
     """The driver takes the N = 1 point of the scaling curve from a plain `python bench.py --gpus 1` and the N > 1 points from
-    torchrun launches: the two launch styles must measure the same thing.  Same steps, sustained region of 1 s each, the torchrun
+    torchrun launches: the two launch styles must measure the same thing.  Same steps, sustained region (--full) of 1 s each, the torchrun
     run with its (one-rank) RCCL exchange and merge inside the timed region: the sustained values agree within 3 % (two processes,
     two clock ramps; the kernels are the same)."""
     import json
@@ -542,8 +542,8 @@ def test_bench_torchrun_single_rank_value_equals_the_plain_run():
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    common = [os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-pmc", "--no-others",
-              "--no-latency", "--sustained-s", "1.0"]
+    common = [os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-pmc",
+              "--no-others", "--no-latency", "--sustained-s", "1.0"]
     vals = {}
     for label, cmd in (("plain", [sys.executable] + common),
                        ("torchrun", [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
@@ -572,8 +572,8 @@ def test_bench_measures_hbm_traffic_live_with_pmc_child_runs(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     E = 1024
     details = tmp_path / "details.json"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--epochs", str(E), "--no-cpu-baseline", "--no-latency",
-           "--sustained-s", "0", "--preroll-s", "0", "--details-json", str(details)]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--epochs", str(E), "--full", "--no-cpu-baseline",
+           "--no-latency", "--sustained-s", "0", "--preroll-s", "0", "--details-json", str(details)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -590,7 +590,7 @@ def test_bench_measures_hbm_traffic_live_with_pmc_child_runs(tmp_path):
     assert x_bytes <= j["roofline"]["traffic"] <= 40 * x_bytes, (j["roofline"]["traffic"], x_bytes)
     assert 0.3 < src["valu_pipe_busy_pmc"] <= 1.0
     assert src["launches_averaged"] >= 3
-    # the default single-GPU headline run also carries the other BASELINE configurations and the complex128 leg (round 3)
+    # the full single-GPU headline run also carries the other BASELINE configurations and the complex128 leg (round 3)
     others = j["other_configs"]
     assert [c["baseline_config"] for c in others] == [3, 4, 5] and not any("error" in c for c in others), others
     for c in others:
@@ -623,6 +623,39 @@ def test_bench_measures_hbm_traffic_live_with_pmc_child_runs(tmp_path):
         if c["bound"] == "hbm":
             sc = c["stream_ceiling"]
             assert sc["measured_in_this_run"] is True and 2000.0 < sc["GBps"] < 8000.0 and (sc.get("exceeded_by_kernel") or 0.0 < sc["frac"] <= 1.0), sc
+
+
+def test_plain_bench_run_is_the_headline_alone(tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` sets up, warms up, times the N steps, writes --dump-outputs and prints the line:
+    the headline fields, none of what --full adds, and at most 30 s of the process's wall time outside its N + W steps."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    details, dump = tmp_path / "details.json", tmp_path / "dump"
+    steps, warmup = 20, 3
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--dump-outputs", str(dump), "--details-json", str(details)]
+    t0 = time.perf_counter()
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    assert j["unit"] == "cells/s" and j["higher_is_better"] is True and j["dtype"] == "f32" and j["metric"].startswith("acquisition cells/s")
+    assert j["steps"] == steps and j["warmup"] == warmup and j["value"] > 1e11
+    assert abs(j["value"] * j["ms_per_step"] * 1e-3 - j["config"]["cells_per_step"]) <= 1e-9 * j["config"]["cells_per_step"]
+    for k in ("other_configs", "reference_precision", "next_rows", "tie_safe", "cpu_baseline_pool", "gpu_over_cpu", "bench_wall_s"):
+        assert k not in j, k
+    assert j["roofline"] is None and j["sustained"] is None and j["host_call_latency"] is None and j["cpu_baseline"] is None
+    assert j["config"]["one_step_in_flight"] is None and j["pipeline"]["per_signal"] is None
+    assert json.load(open(details)) == j                  # nothing cut: the record is the line
+    assert sorted(os.listdir(dump)) == ["gps-l1_code_index.npy", "gps-l1_doppler_index.npy", "gps-l1_metric.npy"]
+    outside = wall - (steps + warmup) * j["ms_per_step"] * 1e-3
+    assert outside < 30.0, (wall, j["ms_per_step"])
 
 
 def test_alternating_between_more_grids_than_the_cache_holds(engine):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Run single legs of bench.py's default line without the rest: tools/bench_legs.py [reference_precision] [next_rows] [stream]"""
+"""Run single legs of bench.py's --full line without the rest: tools/bench_legs.py [reference_precision] [next_rows] [stream]"""
 import json
 import os
 import sys

@@ -13,7 +13,7 @@ timeout 200 python tools/exp_lanes_debug.py --extra-engine 2>&1 | f | tail -4
 echo; echo "== 4. steps / jobs side by side on hardware queues of their own (tools/exp_cfg5_overlap.py)"
 timeout 400 python tools/exp_cfg5_overlap.py 2>&1 | f
 echo; echo "== 5. bench.py --config N --lanes 1 / 2 / 3 (fresh process each)"
-for c in 2 3 4 5; do for Ln in 1 2 3; do timeout 200 python bench.py --config $c --lanes $Ln --steps 20 --warmup 5 --no-others --no-cpu-baseline --no-latency --no-pmc 2>/dev/null | python -c "
+for c in 2 3 4 5; do for Ln in 1 2 3; do timeout 200 python bench.py --config $c --lanes $Ln --steps 20 --warmup 5 --full --no-others --no-cpu-baseline --no-latency --no-pmc 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
