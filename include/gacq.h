@@ -360,6 +360,25 @@ int gacq_correlate_batch_dev(gacq_ctx* ctx, const void* d_x, size_t n, const cha
 int gacq_mix_int8_dev(gacq_ctx* ctx, const void* d_iq_int8, size_t nsamp, double fs, double carrier_offset_hz, void* d_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * The reference's signal-inspection utilities on the device (gacq_spectrum.hip).  Both are asynchronous on the ctx stream; bad
+ * arguments return GACQ_ERR_BAD_ARG before anything is launched.
+ * ------------------------------------------------------------------------------------------- */
+/* Welch power spectrum (spectrum.py:48-57): d_iq_int8 holds nspectra * ns consecutive frames of n interleaved signed 8-bit I/Q samples;
+ * per frame int8 -> float, times d_window (float[n], np.hanning(n) rounded to fp32), complex64 FFT of length n in LDS, re^2 + im^2;
+ * the ns frames of a spectrum are accumulated in fp64, divided by ns, fftshift-ed and written as 10 log10 to d_out_db (double
+ * [nspectra][n]; a bin of power 0 gives -inf).  n: a power of two from 64 to 16384.  split: workgroups per spectrum (0: chosen from
+ * nspectra); the output bits do not depend on it.  d_iq_int8 and d_window must be 16-byte aligned. */
+int gacq_psd_int8_dev(gacq_ctx* ctx, const void* d_iq_int8, size_t nspectra, int n, int ns, const void* d_window, int split, void* d_out_db);
+/* Squaring-loop carrier detector (squaring.py:28-40, gnsstools/squaring.py:14-23, gnsstools/nco.py:30-41): d_iq_int8 holds nchunks
+ * chunks of `chunk` = b*n*m samples.  Sample i of chunk c is multiplied by the table NCO at the 64-bit wrapping phase
+ * floor(d_phase0[c] * 2^60) + i * floor(f * 2^60) (f = -coffset/fs; d_phase0: double[nchunks] on the device, the script's
+ * coffset_phase at each chunk's start), the product rounded to complex64; n consecutive products are summed in fp64 to s, m values of
+ * s*s/n are summed to one output.  d_r: complex128 [nchunks][b]; d_y: the script's int16 stream, round-half-even of 20 re, 20 im
+ * interleaved and clamped to the int16 range; d_clamped: one uint64, the number of clamped values. */
+int gacq_squaring_int8_dev(gacq_ctx* ctx, const void* d_iq_int8, size_t nchunks, size_t chunk, int n, int m, const void* d_phase0, double f,
+                           void* d_r, void* d_y, void* d_clamped);
+
+/* ---------------------------------------------------------------------------------------------
  * Device-resident tracking loops: the template family of the reference's track-*.py (track-gps-l1.py:33-179 and the scripts that
  * differ from it only in the constants below), one workgroup per channel walking its own blocks -- offset and carrier wipe-off
  * (table NCO), early/prompt/late, FLL/PLL/DLL update -- with the state kept on the device between calls.
