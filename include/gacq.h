@@ -475,6 +475,42 @@ void gacq_chiptrack_close(gacq_chiptrack* tr);
 int gacq_track_debug_mix(gacq_ctx* ctx, const void* d_iq_int8, size_t n, double f_offset, double p_offset, double f_carrier,
                          double p_carrier, void* d_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Correlation grid on the raw recording (gacq_corrgrid.hip): the fine search between acquisition and tracking.  For K candidates in
+ * one launch, the prompt correlation over M blocks of n samples, D Doppler hypotheses and P code-phase hypotheses.  With
+ * j = s0 + m n + i the absolute sample index of the candidate's recording,
+ *     f_d = doppler0 + (d - (D-1)/2) df,   cf = (chip_rate + doppler0/ratio) / fs,
+ *     C[k,m,d,p] = sum_{i<n} x[j] exp(-2 pi i frac((carrier_hz + f_d) j / fs)) w(code0 + offsets[p] + cf j)
+ * with w the chip weight of the tracking loops' correlator `kind` (subcarrier phases 2 pos and 12 pos of the same start phase).  The
+ * exponential is the exact one (64-bit phase reduction, no table NCO); the sums are fp32 per lane, fp64 across waves.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gacq_grid_spec {
+  const char* code;                /* code module, e.g. "gps.ca" */
+  int prn;                         /* PRN (GLONASS: 0) */
+  int kind;                        /* correlator kind of gacq_correlate_batch (0 plain .. 5 RZ [0,1]) */
+  int n;                           /* samples per block, >= 1 */
+  int M;                           /* blocks, >= 1 */
+  int D;                           /* Doppler hypotheses, 1..33 */
+  int P;                           /* code-phase hypotheses, 1..33 */
+  double fs;                       /* sample rate of the recording, Hz */
+  double carrier_hz;               /* carrier offset wiped off with every hypothesis (GLONASS: coffset + step * chan) */
+  double chip_rate;                /* nominal chip rate, chips/s */
+  double ratio;                    /* carrier / code frequency ratio; the code rate uses doppler0 for every hypothesis */
+  double doppler0;                 /* centre of the Doppler axis, Hz */
+  double code0;                    /* code phase at sample 0 of the recording, chips */
+  double df;                       /* Doppler step, Hz */
+  long long s0;                    /* first sample of block 0 */
+  const double* offsets;           /* P code offsets in chips, relative to code0 (host memory) */
+} gacq_grid_spec;
+
+/* d_x[k]: candidate k's recording on the device, interleaved signed 8-bit I/Q, avail[k] complex samples (candidates may share one);
+ * nothing outside [0, 2 avail[k]) bytes is read.  out (host): complex128, candidate after candidate, each [M][D][P] -- [K][M][D][P]
+ * when the candidates share M, D and P.  Every argument is checked before anything is launched: s0 + M n > avail returns
+ * GACQ_ERR_SHORT_INPUT; n, M < 1, D or P outside 1..33, a value that is not finite, ratio = 0 GACQ_ERR_BAD_ARG; an unknown code or
+ * PRN GACQ_ERR_UNKNOWN_CODE / GACQ_ERR_BAD_PRN; a code longer than 10240 chips GACQ_ERR_UNSUPPORTED.  One launch on the ctx stream,
+ * one workgroup per (candidate, block); a result's bits depend only on its own candidate and block.  Synchronous. */
+int gacq_corr_grid_dev(gacq_ctx* ctx, const gacq_grid_spec* specs, int K, const void* const* d_x, const long long* avail, double* out);
+
 /* Per-stage GPU time from HIP events recorded on the launch stream (profiling aid for bench.py).
  * Stages: 0 mix/forward, 1 forward FFT (rocFFT), 2 conj-multiply, 3 inverse FFT (rocFFT),
  *         4 magnitude/peak reduce, 5 best-over-Doppler, 6 fused correlate kernel (LDS FFT). */
