@@ -153,6 +153,7 @@ class Engine:
         self._signals = {}
         self._families = {}
         self._live = weakref.WeakSet()      # every AcqSignal created on this context (also user-held ones)
+        self.workspace_bytes = int(workspace_bytes) if workspace_bytes else None      # the caller's workspace limit, if any
         if engine:
             self.set_engine(engine)
         if workspace_bytes:

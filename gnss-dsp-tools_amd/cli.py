@@ -30,21 +30,24 @@ def build_parser(sig):
     return ap
 
 
-_VALUE_OPTS = ("--prn", "--channel", "--doppler-search", "--time", "--device")
+VALUE_OPTS = ("--prn", "--channel", "--doppler-search", "--time", "--device")
 
 
-def _join_option_values(argv):
+def join_option_values(argv, value_opts=VALUE_OPTS):
     """optparse (the reference) accepts '--doppler-search -7000,7000,200' and '--channel -7:7'; argparse would take
     the value for an option because it starts with '-'.  Rewrite 'opt value' as 'opt=value'."""
     out, i = [], 0
     while i < len(argv):
-        if argv[i] in _VALUE_OPTS and i + 1 < len(argv):
+        if argv[i] in value_opts and i + 1 < len(argv):
             out.append(argv[i] + "=" + argv[i + 1])
             i += 2
         else:
             out.append(argv[i])
             i += 1
     return out
+
+
+_join_option_values = join_option_values
 
 
 def run(name, argv, out=sys.stdout):

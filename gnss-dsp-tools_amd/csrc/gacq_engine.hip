@@ -560,6 +560,10 @@ void gacq_destroy(gacq_ctx* ctx) {
   if (ctx->pin_x.p) (void)hipHostFree(ctx->pin_x.p);
   if (ctx->pin_peaks.p) (void)hipHostFree(ctx->pin_peaks.p);
   if (ctx->pin_tie.p) (void)hipHostFree(ctx->pin_tie.p);
+  for (int k = 0; k < 2; k++) {
+    if (ctx->pin_fold[k].p) (void)hipHostFree(ctx->pin_fold[k].p);
+    if (ctx->fold_done[k]) (void)hipEventDestroy(ctx->fold_done[k]);
+  }
   if (ctx->bar_x.p) (void)hipFree(ctx->bar_x.p);
   if (ctx->bar_s.p) (void)hipFree(ctx->bar_s.p);
   for (auto& sl : ctx->grid_slots) for (DevBuf* b : {&sl.dfreq, &sl.dfset, &sl.ditems}) if (b->p) (void)hipFree(b->p);

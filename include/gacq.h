@@ -511,6 +511,22 @@ typedef struct gacq_grid_spec {
  * one workgroup per (candidate, block); a result's bits depend only on its own candidate and block.  Synchronous. */
 int gacq_corr_grid_dev(gacq_ctx* ctx, const gacq_grid_spec* specs, int K, const void* const* d_x, const long long* avail, double* out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Coherent fold ahead of the search (gacq_cohfold.hip): M code periods summed under H sign hypotheses, per Doppler value, so that the
+ * search of a folded row is the coherent search over M periods (correlation is linear).  With x complex64 on the device (wide != 0:
+ * complex128, rounded once), j0 the absolute sample index of x[0], D Doppler values f_d (Hz), H patterns W[h][m] in {-1, 0, +1} and
+ * a start table start[d][m] in samples of x (both row-major, host memory),
+ *     y[d,h,i] = sum_{m<M} W[h,m] x[start[d,m] + i] exp(-2 pi i frac(f_d (j0 + start[d,m] + i) / fs)),   0 <= i < n_out.
+ * d_y: complex64 [D][H][n_out] on the device, contiguous.  The exponential is exact per sample (64-bit fixed-point phase reduced
+ * before it becomes fp32; no table NCO, nothing extrapolated along the Doppler axis); the sum is fp32 in the order of m.  The bits of
+ * y[d,h,:] depend on row d's inputs and on W[h] alone -- not on D, H, or how a caller splits the rows over calls.
+ * Every argument is checked before anything is allocated or launched: n_out, M, D or H < 1, M > 128, H > 256, f_d or fs not finite,
+ * fs <= 0, a W entry outside -1..1, |j0| > 2^62 GACQ_ERR_BAD_ARG; start[d][m] < 0 or start[d][m] + n_out > avail (complex samples at
+ * d_x) GACQ_ERR_SHORT_INPUT.  One launch on the ctx stream; asynchronous.
+ * ------------------------------------------------------------------------------------------- */
+int gacq_fold_dev(gacq_ctx* ctx, const void* d_x, int wide, long long avail, int n_out, int M, int D, int H, const long long* start,
+                  const double* f_d, double fs, long long j0, const signed char* W, void* d_y);
+
 /* Per-stage GPU time from HIP events recorded on the launch stream (profiling aid for bench.py).
  * Stages: 0 mix/forward, 1 forward FFT (rocFFT), 2 conj-multiply, 3 inverse FFT (rocFFT),
  *         4 magnitude/peak reduce, 5 best-over-Doppler, 6 fused correlate kernel (LDS FFT). */
