@@ -13,14 +13,13 @@ sequential fp64 sum in sample order.
 prints the script's lines and writes ./track-chips.dat, as the scripts do.
 """
 import ctypes
-import optparse
 import sys
 
 import numpy as np
 
 from . import _native as nat
-from . import acquire
 from . import codes
+from . import track
 from . import trackloop
 from .trackloop import RECORD_DTYPE, STATE_DTYPE, Channel, Tracker, TrackSpec  # noqa: F401  (re-exported)
 
@@ -37,18 +36,7 @@ def chip_channel_spec(ch):
     """gacq_track_spec of a B2b channel: trackloop.channel_spec's arithmetic with CHIP_TRACKERS' constants."""
     if ch.name not in CHIP_TRACKERS:
         raise KeyError("unknown chip tracker %r (%s)" % (ch.name, ", ".join(sorted(CHIP_TRACKERS))))
-    t = CHIP_TRACKERS[ch.name]
-    wide, narrow = float(ch.loop_dwells[0]), float(ch.loop_dwells[1])
-    phase = 0.0
-    if ch.carrier_phase is not None:
-        wide, narrow = 0.0, 0.0                  # loop_dwells = 0,0
-        phase = float(ch.carrier_phase)
-    return TrackSpec(code=t.code.encode(), prn=int(ch.prn), kind=t.kind, subs=t.subs, fixed_pll=0, glonass=0, pad=0, fs=float(ch.fs),
-                     period=t.period, rate=t.rate, ratio=t.ratio, spacing=t.spacing, chip_rate=float(codes.chip_rate(t.code)),
-                     fll_k_wide=t.fll[0], fll_k_narrow=t.fll[1], pll_k1=float(t.pll[0]), pll_k2=float(t.pll[1]),
-                     dll_k1=float(t.dll[0]), dll_k2=float(t.dll[1]), coffset=float(ch.coffset), fm=0.0,
-                     code_offset=float(ch.code_offset), doppler=float(ch.doppler), carrier_phase=phase, dwell_wide=wide,
-                     dwell_narrow=narrow)
+    return trackloop.channel_spec(ch, CHIP_TRACKERS)
 
 
 class ChipTrackLoop(trackloop.TrackLoop):
@@ -62,6 +50,8 @@ class ChipTrackLoop(trackloop.TrackLoop):
         self.L = [codes.code_length(CHIP_TRACKERS[c.name].code) if c.name in CHIP_TRACKERS else 0 for c in channels]
         super().__init__(channels, engine, max_records)
 
+    _lib = "gacq_chiptrack"
+
     @staticmethod
     def _trackers():
         return CHIP_TRACKERS
@@ -72,28 +62,15 @@ class ChipTrackLoop(trackloop.TrackLoop):
 
     def _open(self):
         h = ctypes.c_void_p()
-        nat.check(nat.lib.gacq_chiptrack_open(self.eng._ctx, self._specs, self.K, self.accum_after.ctypes.data_as(ctypes.c_void_p),
-                                              ctypes.byref(h)), self.eng._ctx)
+        nat.check(self._call("open", self.eng._ctx, self._specs, self.K, self.accum_after.ctypes.data_as(ctypes.c_void_p), ctypes.byref(h)),
+                  self.eng._ctx)
         return h
-
-    def close(self):
-        if self._h:
-            nat.lib.gacq_chiptrack_close(self._h)
-            self._h = None
-
-    def state(self, k):
-        out = np.zeros(1, dtype=STATE_DTYPE)
-        nat.check(nat.lib.gacq_chiptrack_state(self._h, k, out.ctypes.data_as(ctypes.c_void_p)), self.eng._ctx)
-        return out[0]
 
     def chips(self, k):
         """Channel k's chip accumulator: complex128[L], the script's s.chips."""
         out = np.zeros(2 * self.L[k], dtype=np.float64)
-        nat.check(nat.lib.gacq_chiptrack_chips(self._h, k, out.ctypes.data_as(ctypes.c_void_p)), self.eng._ctx)
+        nat.check(self._call("chips", self._h, k, out.ctypes.data_as(ctypes.c_void_p)), self.eng._ctx)
         return out.view(np.complex128)
-
-    def _run_dev(self, ptrs, base, avail, recs, cap, counts, status):
-        return nat.lib.gacq_chiptrack_run_dev(self._h, ptrs, base, avail, self.max_records, recs, cap, counts, status)
 
 
 def format_chips(chips):
@@ -103,50 +80,21 @@ def format_chips(chips):
 
 def format_lines(name, recs):
     """The script's output lines ('%d %f %f %f %f %f %f %f %f')."""
-    cr = float(codes.chip_rate(CHIP_TRACKERS[name].code))
-    out = []
-    for r in recs:
-        p = complex(float(r["p_re"]), float(r["p_im"]))
-        v = (int(r["block"]), np.real(p), np.imag(p), float(r["carrier_f"]), float(r["code_f"]) - cr, (180 / np.pi) * np.angle(p),
-             float(r["early"]), float(r["prompt"]), float(r["late"]))
-        out.append('%d %f %f %f %f %f %f %f %f' % v)
-    return out
+    return trackloop.format_lines(name, recs, trackers=CHIP_TRACKERS)
 
 
-def track_file(name, path, fs, coffset, prn, doppler, code_offset, loop_dwells=(500.0, 500.0), carrier_phase=None, engine=None,
-               accum_after=ACCUM_AFTER):
-    """One script run on one file: returns (records, output lines, chips)."""
-    ch = Channel(name, fs, coffset, prn, doppler, code_offset, tuple(loop_dwells), carrier_phase)
-    eng = engine or acquire.default_engine()
-    tl = ChipTrackLoop([ch], eng, accum_after=accum_after)
-    try:
-        recs = tl.run([trackloop.load_int8(path, eng.device)])[0]
-        chips = tl.chips(0)
-    finally:
-        tl.close()
-    return recs, format_lines(name, recs), chips
+def track_file(*args, accum_after=ACCUM_AFTER, **kw):
+    """One script run on one file, trackloop.track_file's arguments: returns (records, output lines, chips)."""
+    return trackloop.track_file(*args, loop=ChipTrackLoop, accum_after=accum_after, **kw)
 
 
 def build_parser(name):
-    p = optparse.OptionParser(usage="%s [options] input_filename sample_rate carrier_offset PRN doppler code_offset" % name)
-    p.disable_interspersed_args()
-    p.add_option("--loop-dwells", default="500,500", help="initial time intervals for wide FLL, then narrow FLL, in milliseconds "
-                                                          "(default %default)")
-    p.add_option("--carrier-phase", help="initial carrier phase in cycles (disables FLL: uses PLL from the start)")
-    return p
+    return track.build_parser(name, CHIP_TRACKERS)
 
 
 def parse(name, argv):
     """(path, Channel) of one command line (argv after the tracker name), with the script's own argument conversions."""
-    if name not in CHIP_TRACKERS:
-        raise SystemExit("unknown chip tracker %r; the chip trackers: %s" % (name, " ".join(sorted(CHIP_TRACKERS))))
-    options, args = build_parser(name).parse_args(list(argv))
-    if len(args) < 6:
-        raise SystemExit("%s: need input_filename sample_rate carrier_offset PRN doppler code_offset" % name)
-    dwells = tuple(map(float, options.loop_dwells.split(",")))        # util.parse_list_floats
-    phase = float(options.carrier_phase) if options.carrier_phase is not None else None
-    ch = Channel(name, float(args[1]), float(args[2]), int(args[3]), float(args[4]), float(args[5]), dwells, phase)
-    return args[0], ch
+    return track.parse(name, argv, CHIP_TRACKERS, "chip tracker")
 
 
 def run(name, argv, out=sys.stdout, chips_path=CHIPS_FILE):

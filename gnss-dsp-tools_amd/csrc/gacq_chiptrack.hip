@@ -276,13 +276,11 @@ __global__ __launch_bounds__(kCtBlock) void chip_track_kernel(const TlSpec* __re
 
 }  // namespace
 
-struct gacq_chiptrack {
-  gacq_ctx* ctx = nullptr;
-  int K = 0;
-  int subs_max = 1;
+#include "gacq_trackhost.h"
+
+struct gacq_chiptrack : TlHandle {
   std::vector<int> L;
-  DevBuf d_specs, d_runs, d_states, d_recs, d_thr, d_bins;
-  const double2* d_tab = nullptr;
+  gacq::DevBuf d_thr, d_bins;
 };
 
 extern "C" int gacq_chiptrack_open(gacq_ctx* ctx, const gacq_track_spec* specs, int K, const long long* accum_after, gacq_chiptrack** out) {
@@ -290,7 +288,6 @@ extern "C" int gacq_chiptrack_open(gacq_ctx* ctx, const gacq_track_spec* specs, 
   *out = nullptr;
   if (!specs || K <= 0 || !accum_after)
     return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_chiptrack_open: need at least one channel and its threshold (K = %d)", K);
-  std::vector<int> Ls(K);
   for (int k = 0; k < K; k++) {
     const gacq_track_spec& s = specs[k];
     if (!s.code) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_chiptrack_open: channel %d has no code", k);
@@ -299,51 +296,20 @@ extern "C" int gacq_chiptrack_open(gacq_ctx* ctx, const gacq_track_spec* specs, 
     if (s.kind != 0 || L > kCtMaxChips || s.glonass)
       return set_error(ctx, GACQ_ERR_UNSUPPORTED, "gacq_chiptrack_open: channel %d: the chip accumulator takes plain codes (kind 0) of at most "
                        "%d chips, not '%s' kind %d", k, kCtMaxChips, s.code, s.kind);
-    Ls[k] = L;
   }
-  // the loop's own checks, spec layout and code-boundary alignment are the template's: open one and keep its device state
-  gacq_track* tr = nullptr;
-  int rc = gacq_track_open(ctx, specs, K, &tr);
+  // the loop's own checks, spec layout and code-boundary alignment are the template's and report under its name.  With no GLONASS
+  // channel past the check above, every offset NCO step is floor(-coffset / fs * 2^60)
+  static const TlLimits lim = {"gacq_track_open", 0x3f, 64, kCtMaxChips, HUGE_VAL, false};
+  TlPrep p;
+  int rc = tl_prepare(ctx, lim, specs, K, p);
   if (rc != GACQ_OK) return rc;
   GACQ_DEVICE(ctx);
   gacq_chiptrack* h = new gacq_chiptrack();
-  h->ctx = ctx;
-  h->K = K;
-  h->L = Ls;
-  // struct gacq_track is private to gacq_trackloop.hip: read the template handle's state back through the ABI
-  std::vector<gacq_track_chstate> init(K);
-  for (int k = 0; k < K && rc == GACQ_OK; k++) rc = gacq_track_state(tr, k, &init[k]);
-  gacq_track_close(tr);
-  std::vector<TlSpec> ts(K);
-  for (int k = 0; k < K && rc == GACQ_OK; k++) {
-    const gacq_track_spec& s = specs[k];
-    std::vector<uint8_t> chips(Ls[k]);
-    rc = gacq_code_chips(s.code, s.prn, chips.data(), Ls[k]);
-    if (rc < 0) {
-      rc = set_error(ctx, rc, "gacq_chiptrack_open: channel %d: no PRN %d in '%s'", k, s.prn, s.code);
-      break;
-    }
-    const void* d = nullptr;
-    rc = table_cache(ctx, std::string("chips:") + s.code + ":" + std::to_string(s.prn), chips.data(), chips.size(), &d);
-    TlSpec& t = ts[k];
-    t.chips = (const uint8_t*)d;
-    t.L = Ls[k]; t.kind = s.kind; t.subs = s.subs; t.fixed_pll = s.fixed_pll ? 1 : 0; t.glonass = 0; t.pad = 0;
-    t.fs = s.fs; t.period = s.period; t.ratio = s.ratio; t.spacing = s.spacing;
-    t.fll_k_wide = s.fll_k_wide; t.fll_k_narrow = s.fll_k_narrow; t.pll_k1 = s.pll_k1; t.pll_k2 = s.pll_k2; t.dll_k1 = s.dll_k1; t.dll_k2 = s.dll_k2;
-    t.coffset = s.coffset; t.fm = s.fm;
-    t.dfo = (long long)std::floor((-s.coffset / s.fs) * kTwo60);
-    t.dwell_wide = s.dwell_wide; t.dwell_narrow = s.dwell_narrow;
-    h->subs_max = std::max(h->subs_max, s.subs);
-  }
-  if (rc == GACQ_OK) rc = nco_table(ctx, &h->d_tab);
-  if (rc == GACQ_OK) rc = ensure(ctx, h->d_specs, sizeof(TlSpec) * K);
-  if (rc == GACQ_OK) rc = ensure(ctx, h->d_runs, sizeof(TlRun) * K);
-  if (rc == GACQ_OK) rc = ensure(ctx, h->d_states, sizeof(gacq_track_chstate) * K);
+  for (const TlSpec& t : p.specs) h->L.push_back(t.L);
+  rc = tl_upload(ctx, "gacq_chiptrack_open", p, h);
   if (rc == GACQ_OK) rc = ensure(ctx, h->d_thr, sizeof(long long) * K);
   if (rc == GACQ_OK) rc = ensure(ctx, h->d_bins, sizeof(double2) * kCtMaxChips * (size_t)K);
-  if (rc == GACQ_OK && (hipMemcpy(h->d_specs.p, ts.data(), sizeof(TlSpec) * K, hipMemcpyHostToDevice) != hipSuccess ||
-                        hipMemcpy(h->d_states.p, init.data(), sizeof(gacq_track_chstate) * K, hipMemcpyHostToDevice) != hipSuccess ||
-                        hipMemcpy(h->d_thr.p, accum_after, sizeof(long long) * K, hipMemcpyHostToDevice) != hipSuccess ||
+  if (rc == GACQ_OK && (hipMemcpy(h->d_thr.p, accum_after, sizeof(long long) * K, hipMemcpyHostToDevice) != hipSuccess ||
                         hipMemset(h->d_bins.p, 0, sizeof(double2) * kCtMaxChips * (size_t)K) != hipSuccess))
     rc = set_error(ctx, GACQ_ERR_HIP, "gacq_chiptrack_open: upload failed");
   if (rc != GACQ_OK) {
@@ -356,53 +322,14 @@ extern "C" int gacq_chiptrack_open(gacq_ctx* ctx, const gacq_track_spec* specs, 
 
 extern "C" int gacq_chiptrack_run_dev(gacq_chiptrack* h, const void* const* d_x, const long long* base, const long long* avail,
                                       int max_records, gacq_track_record* recs, int rec_cap, int* counts, int* status) {
-  if (!h) return GACQ_ERR_BAD_ARG;
-  gacq_ctx* ctx = h->ctx;
-  if (!d_x || !base || !avail || !recs || !counts || !status || max_records < h->subs_max || rec_cap < max_records)
-    return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_chiptrack_run_dev: bad argument (need %d <= max_records <= rec_cap)", h->subs_max);
-  const int K = h->K;
-  std::vector<gacq_track_chstate> now(K);
-  GACQ_DEVICE(ctx);
-  hipStream_t stream = ctx->stream;
-  GACQ_HIP(ctx, hipMemcpyAsync(now.data(), h->d_states.p, sizeof(gacq_track_chstate) * K, hipMemcpyDeviceToHost, stream));
-  GACQ_HIP(ctx, hipStreamSynchronize(stream));
-  std::vector<TlRun> runs(K);
-  for (int k = 0; k < K; k++) {
-    if (!d_x[k] || base[k] < 0 || avail[k] < 0) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_chiptrack_run_dev: channel %d: bad samples", k);
-    if (base[k] > now[k].pos)
-      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_chiptrack_run_dev: channel %d: samples start at %lld, the next block at %lld", k,
-                       base[k], now[k].pos);
-    runs[k].x = (const int8_t*)d_x[k];
-    runs[k].base = base[k];
-    runs[k].end = base[k] + avail[k];
-  }
-  int rc;
-  if ((rc = ensure(ctx, h->d_recs, sizeof(gacq_track_record) * (size_t)K * rec_cap)) != GACQ_OK) return rc;
-  GACQ_HIP(ctx, hipMemcpyAsync(h->d_runs.p, runs.data(), sizeof(TlRun) * K, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(chip_track_kernel, dim3((unsigned)K), dim3(kCtBlock), 0, stream, (const TlSpec*)h->d_specs.p, (const TlRun*)h->d_runs.p,
-                     (gacq_track_chstate*)h->d_states.p, h->d_tab, (const long long*)h->d_thr.p, (double2*)h->d_bins.p,
-                     (gacq_track_record*)h->d_recs.p, rec_cap, max_records);
-  GACQ_HIP(ctx, hipGetLastError());
-  GACQ_HIP(ctx, hipMemcpyAsync(now.data(), h->d_states.p, sizeof(gacq_track_chstate) * K, hipMemcpyDeviceToHost, stream));
-  GACQ_HIP(ctx, hipMemcpyAsync(recs, h->d_recs.p, sizeof(gacq_track_record) * (size_t)K * rec_cap, hipMemcpyDeviceToHost, stream));
-  GACQ_HIP(ctx, hipStreamSynchronize(stream));
-  for (int k = 0; k < K; k++) {
-    status[k] = now[k].status;
-    counts[k] = now[k].last_records;
-  }
-  return GACQ_OK;
+  return tl_run(h, "gacq_chiptrack_run_dev", false, d_x, base, avail, max_records, recs, rec_cap, counts, status, [&](hipStream_t stream) {
+    hipLaunchKernelGGL(chip_track_kernel, dim3((unsigned)h->K), dim3(kCtBlock), 0, stream, (const TlSpec*)h->d_specs.p, (const TlRun*)h->d_runs.p,
+                       (gacq_track_chstate*)h->d_states.p, h->d_tab, (const long long*)h->d_thr.p, (double2*)h->d_bins.p,
+                       (gacq_track_record*)h->d_recs.p, rec_cap, max_records);
+  });
 }
 
-extern "C" int gacq_chiptrack_state(gacq_chiptrack* h, int k, gacq_track_chstate* out) {
-  if (!h) return GACQ_ERR_BAD_ARG;
-  gacq_ctx* ctx = h->ctx;
-  if (!out || k < 0 || k >= h->K) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_chiptrack_state: bad channel %d", k);
-  GACQ_DEVICE(ctx);
-  GACQ_HIP(ctx, hipMemcpyAsync(out, (const gacq_track_chstate*)h->d_states.p + k, sizeof(gacq_track_chstate), hipMemcpyDeviceToHost,
-                               ctx->stream));
-  GACQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return GACQ_OK;
-}
+extern "C" int gacq_chiptrack_state(gacq_chiptrack* h, int k, gacq_track_chstate* out) { return tl_state(h, "gacq_chiptrack_state", k, out); }
 
 extern "C" int gacq_chiptrack_chips(gacq_chiptrack* h, int k, double* out) {
   if (!h) return GACQ_ERR_BAD_ARG;
@@ -416,12 +343,5 @@ extern "C" int gacq_chiptrack_chips(gacq_chiptrack* h, int k, double* out) {
 }
 
 extern "C" void gacq_chiptrack_close(gacq_chiptrack* h) {
-  if (!h) return;
-  {
-    DeviceGuard g(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    for (DevBuf* b : {&h->d_specs, &h->d_runs, &h->d_states, &h->d_recs, &h->d_thr, &h->d_bins})
-      if (b->p) (void)hipFree(b->p);
-  }
-  delete h;
+  if (h) tl_close(h, {&h->d_thr, &h->d_bins});
 }

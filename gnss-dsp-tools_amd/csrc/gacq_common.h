@@ -167,6 +167,27 @@ int ensure_pinned(gacq_ctx* ctx, DevBuf& b, size_t bytes);      // hipHostMalloc
 int twiddle_cache(gacq_ctx* ctx, const std::string& key, int N, int count, const float2** out);
 // arbitrary constant bytes cached per ctx under `key` (uploaded on first use)
 int table_cache(gacq_ctx* ctx, const std::string& key, const void* host, size_t bytes, const void** out);
+// The chip table of (code, PRN), one byte per chip, cached per ctx under "chips:<code>:<prn>" and shared by the tracking loops, the
+// correlators and the long-code search.  In two steps, because callers check all their channels before they touch the device:
+// chip_table_host generates the L chips on the host and returns gacq_code_chips' code -- with `lazy`, only when the cache lacks them
+// (GLONASS P is 5.11 M chips), so a bad PRN is then reported only on first use; chip_table_dev uploads them or finds the cached table.
+struct ChipTable {
+  std::string key;
+  std::vector<uint8_t> chips;
+};
+inline int chip_table_host(const gacq_ctx* ctx, const char* code, int prn, int L, bool lazy, ChipTable& t) {
+  t.key = std::string("chips:") + code + ":" + std::to_string(prn);
+  if (lazy && ctx->tables.count(t.key)) return GACQ_OK;
+  t.chips.resize(L);
+  const int rc = gacq_code_chips(code, prn, t.chips.data(), L);
+  return rc < 0 ? rc : GACQ_OK;
+}
+inline int chip_table_dev(gacq_ctx* ctx, const ChipTable& t, const uint8_t** out) {
+  const void* d = nullptr;
+  const int rc = table_cache(ctx, t.key, t.chips.data(), t.chips.size(), &d);
+  *out = (const uint8_t*)d;
+  return rc;
+}
 int fft_exec(gacq_ctx* ctx, int N, long batch, bool inverse, void* data, bool fp64 = false);
 // Which kernels serve a search: plan_search (gacq_engine.hip) decides it once per launch from the engine, the FFT length, the grid
 // and the options; launch_search and verify_search switch on it.

@@ -22,7 +22,6 @@
 
 #include <cmath>
 #include <cstring>
-#include <string>
 #include <vector>
 
 using namespace gacq;
@@ -197,8 +196,7 @@ extern "C" int gacq_corr_grid_dev(gacq_ctx* ctx, const gacq_grid_spec* specs, in
   if (!specs || !d_x || !avail || !out || K < 1) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_corr_grid_dev: NULL argument or K = %d < 1", K);
   // every candidate is checked before anything is allocated or launched
   std::vector<CgSpec> cs(K);
-  std::vector<std::string> keys(K);
-  std::vector<std::vector<uint8_t>> chips(K);
+  std::vector<ChipTable> tabs(K);
   long long nout = 0, nwg = 0;
   int short_k = -1;
   for (int k = 0; k < K; k++) {
@@ -207,8 +205,7 @@ extern "C" int gacq_corr_grid_dev(gacq_ctx* ctx, const gacq_grid_spec* specs, in
     const int L = gacq_code_length(s.code);
     if (L < 0) return set_error(ctx, GACQ_ERR_UNKNOWN_CODE, "gacq_corr_grid_dev: candidate %d: unknown code '%s'", k, s.code);
     if (L > kCgMaxChips) return set_error(ctx, GACQ_ERR_UNSUPPORTED, "gacq_corr_grid_dev: candidate %d: code '%s' is longer than %d chips", k, s.code, kCgMaxChips);
-    chips[k].resize(L);
-    const int rc = gacq_code_chips(s.code, s.prn, chips[k].data(), L);
+    const int rc = chip_table_host(ctx, s.code, s.prn, L, false, tabs[k]);
     if (rc < 0) return set_error(ctx, rc, "gacq_corr_grid_dev: candidate %d: no PRN %d in '%s'", k, s.prn, s.code);
     if (s.kind < 0 || s.kind > 5) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_corr_grid_dev: candidate %d: correlator kind %d", k, s.kind);
     const bool fin = std::isfinite(s.fs) && std::isfinite(s.carrier_hz) && std::isfinite(s.chip_rate) && std::isfinite(s.ratio) &&
@@ -251,7 +248,6 @@ extern "C" int gacq_corr_grid_dev(gacq_ctx* ctx, const gacq_grid_spec* specs, in
     c.wg0 = (int)nwg;
     nwg += s.M;
     nout += (long long)s.M * s.D * s.P;
-    keys[k] = std::string("chips:") + s.code + ":" + std::to_string(s.prn);
   }
   if (short_k >= 0) {
     const gacq_grid_spec& s = specs[short_k];
@@ -261,11 +257,8 @@ extern "C" int gacq_corr_grid_dev(gacq_ctx* ctx, const gacq_grid_spec* specs, in
   GACQ_DEVICE(ctx);
   hipStream_t stream = ctx->stream;
   int rc;
-  for (int k = 0; k < K; k++) {
-    const void* d = nullptr;
-    if ((rc = table_cache(ctx, keys[k], chips[k].data(), chips[k].size(), &d)) != GACQ_OK) return rc;
-    cs[k].chips = (const uint8_t*)d;
-  }
+  for (int k = 0; k < K; k++)
+    if ((rc = chip_table_dev(ctx, tabs[k], &cs[k].chips)) != GACQ_OK) return rc;
   DevBuf& d_specs = ctx->tables["corrgrid:specs"];
   DevBuf& d_out = ctx->tables["corrgrid:out"];
   if ((rc = ensure(ctx, d_specs, sizeof(CgSpec) * (size_t)K)) != GACQ_OK) return rc;

@@ -103,17 +103,11 @@ __global__ void longcode_finish_kernel(const double2* __restrict__ partial, doub
 int device_chips(gacq_ctx* ctx, const char* code, int prn, const uint8_t** out, long* L) {
   const int len = gacq_code_length(code);
   if (len < 0) return set_error(ctx, GACQ_ERR_UNKNOWN_CODE, "long-code search: unknown code '%s'", code);
-  const std::string key = std::string("chips:") + code + ":" + std::to_string(prn);
   *L = len;
-  auto it = ctx->tables.find(key);
-  if (it != ctx->tables.end()) { *out = (const uint8_t*)it->second.p; return GACQ_OK; }
-  std::vector<uint8_t> h(len);
-  const int rc = gacq_code_chips(code, prn, h.data(), len);
+  ChipTable t;
+  const int rc = chip_table_host(ctx, code, prn, len, true, t);
   if (rc < 0) return set_error(ctx, rc, "long-code search: no PRN %d in '%s'", prn, code);
-  const void* p = nullptr;
-  const int rc2 = table_cache(ctx, key, h.data(), (size_t)len, &p);
-  *out = (const uint8_t*)p;
-  return rc2;
+  return chip_table_dev(ctx, t, out);
 }
 
 }  // namespace

@@ -28,7 +28,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -238,156 +237,25 @@ __global__ __launch_bounds__(kLtBlock) void longtrack_kernel(const TlSpec* __res
 
 }  // namespace
 
-struct gacq_longtrack {
-  gacq_ctx* ctx = nullptr;
-  int K = 0;
-  int subs_max = 1;
-  DevBuf d_specs, d_runs, d_states, d_recs;
-  const double2* d_tab = nullptr;
-};
+#include "gacq_trackhost.h"
 
+struct gacq_longtrack : TlHandle {};
+
+// no limit on the code's length: the kernel reads the chips through its LDS window.  A table is generated only when the context's
+// cache lacks it (5.11 M chips for GLONASS P)
 extern "C" int gacq_longtrack_open(gacq_ctx* ctx, const gacq_track_spec* specs, int K, gacq_longtrack** out) {
-  if (!ctx || !out) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_open: NULL argument");
-  *out = nullptr;
-  if (!specs || K <= 0) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_open: need at least one channel (K = %d)", K);
-  std::vector<TlSpec> ts(K);
-  std::vector<gacq_track_chstate> init(K);
-  std::vector<std::string> keys(K);
-  std::map<std::string, std::vector<uint8_t>> chips;      // tables not yet in the context's cache, one per code and PRN
-  int subs_max = 1;
-  for (int k = 0; k < K; k++) {
-    const gacq_track_spec& s = specs[k];
-    if (!s.code) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_open: channel %d has no code", k);
-    const int L = gacq_code_length(s.code);
-    if (L < 0) return set_error(ctx, GACQ_ERR_UNKNOWN_CODE, "gacq_longtrack_open: channel %d: unknown code '%s'", k, s.code);
-    const bool fin = std::isfinite(s.fs) && std::isfinite(s.period) && std::isfinite(s.rate) && std::isfinite(s.ratio) &&
-                     std::isfinite(s.spacing) && std::isfinite(s.coffset) && std::isfinite(s.fm) && std::isfinite(s.code_offset) &&
-                     std::isfinite(s.doppler) && std::isfinite(s.carrier_phase) && std::isfinite(s.chip_rate);
-    if (!fin || !(s.fs > 0.0)) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_open: channel %d: bad sample rate or parameter", k);
-    if (!(s.code_offset >= 0.0 && s.code_offset < (double)L))
-      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_open: channel %d: code offset %g outside [0, %d)", k, s.code_offset, L);
-    if (!(s.kind == 0 || s.kind == 4 || s.kind == 5) || s.subs < 1 || s.subs > kMaxSubs || !(s.period > 0.0) || !(s.rate > 0.0) ||
-        s.ratio == 0.0 || !(s.spacing >= 0.0) || !(s.spacing < 0.25 * kWinChips))
-      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_open: channel %d: bad tracker parameters", k);
-    const double fo = s.glonass ? s.fm : -s.coffset / s.fs;
-    if (!(std::fabs(fo) < 7.0) || !(std::fabs(s.carrier_phase) < 7.0) || !(std::fabs(s.doppler / s.fs) < 7.0))
-      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_open: channel %d: NCO frequency or phase out of range", k);
-    keys[k] = std::string("chips:") + s.code + ":" + std::to_string(s.prn);
-    if (!ctx->tables.count(keys[k]) && !chips.count(keys[k])) {
-      std::vector<uint8_t> c(L);
-      const int rc = gacq_code_chips(s.code, s.prn, c.data(), L);
-      if (rc < 0) return set_error(ctx, rc, "gacq_longtrack_open: channel %d: no PRN %d in '%s'", k, s.prn, s.code);
-      chips.emplace(keys[k], std::move(c));
-    }
-    TlSpec& t = ts[k];
-    t.L = L; t.kind = s.kind; t.subs = s.subs; t.fixed_pll = s.fixed_pll ? 1 : 0; t.glonass = s.glonass ? 1 : 0; t.pad = 0;
-    t.fs = s.fs; t.period = s.period; t.ratio = s.ratio; t.spacing = s.spacing;
-    t.fll_k_wide = s.fll_k_wide; t.fll_k_narrow = s.fll_k_narrow; t.pll_k1 = s.pll_k1; t.pll_k2 = s.pll_k2; t.dll_k1 = s.dll_k1; t.dll_k2 = s.dll_k2;
-    t.coffset = s.coffset; t.fm = s.fm;
-    t.dfo = (long long)std::floor(fo * kTwo60);
-    t.dwell_wide = s.dwell_wide; t.dwell_narrow = s.dwell_narrow;
-    // alignment with the code boundary (track-gps-l2cl.py:133-136), on the host: n = int(fs*period*((L-code_offset)/L)),
-    // code_offset += n*rate*L/fs
-    const long long n0 = (long long)(s.fs * s.period * (((double)L - s.code_offset) / (double)L));
-    gacq_track_chstate& g = init[k];
-    std::memset(&g, 0, sizeof(g));
-    g.code_p = s.code_offset + n0 * s.rate * (double)L / s.fs;
-    g.code_f = s.chip_rate;
-    g.carrier_p = s.carrier_phase;
-    g.carrier_f = s.doppler;
-    g.mode = s.fixed_pll ? kModePll : kModeFllWide;
-    g.pos = n0;
-    subs_max = std::max(subs_max, s.subs);
-  }
-  GACQ_DEVICE(ctx);
-  gacq_longtrack* h = new gacq_longtrack();
-  h->ctx = ctx;
-  h->K = K;
-  h->subs_max = subs_max;
-  int rc = GACQ_OK;
-  for (int k = 0; k < K && rc == GACQ_OK; k++) {
-    const void* d = nullptr;
-    auto it = chips.find(keys[k]);
-    rc = table_cache(ctx, keys[k], it == chips.end() ? nullptr : it->second.data(), it == chips.end() ? 0 : it->second.size(), &d);
-    ts[k].chips = (const uint8_t*)d;
-  }
-  if (rc == GACQ_OK) rc = nco_table(ctx, &h->d_tab);
-  if (rc == GACQ_OK) rc = ensure(ctx, h->d_specs, sizeof(TlSpec) * K);
-  if (rc == GACQ_OK) rc = ensure(ctx, h->d_runs, sizeof(TlRun) * K);
-  if (rc == GACQ_OK) rc = ensure(ctx, h->d_states, sizeof(gacq_track_chstate) * K);
-  if (rc == GACQ_OK && hipMemcpy(h->d_specs.p, ts.data(), sizeof(TlSpec) * K, hipMemcpyHostToDevice) != hipSuccess)
-    rc = set_error(ctx, GACQ_ERR_HIP, "gacq_longtrack_open: upload failed");
-  if (rc == GACQ_OK && hipMemcpy(h->d_states.p, init.data(), sizeof(gacq_track_chstate) * K, hipMemcpyHostToDevice) != hipSuccess)
-    rc = set_error(ctx, GACQ_ERR_HIP, "gacq_longtrack_open: upload failed");
-  if (rc != GACQ_OK) {
-    gacq_longtrack_close(h);
-    return rc;
-  }
-  *out = h;
-  return GACQ_OK;
+  static const TlLimits lim = {"gacq_longtrack_open", 1u << 0 | 1u << 4 | 1u << 5, kMaxSubs, 0, 0.25 * kWinChips, true};
+  return tl_open(ctx, lim, specs, K, out);
 }
 
 extern "C" int gacq_longtrack_run_dev(gacq_longtrack* h, const void* const* d_x, const long long* base, const long long* avail,
                                       int max_records, gacq_track_record* recs, int rec_cap, int* counts, int* status) {
-  if (!h) return GACQ_ERR_BAD_ARG;
-  gacq_ctx* ctx = h->ctx;
-  if (!d_x || !base || !avail || !recs || !counts || !status || max_records < h->subs_max || rec_cap < max_records)
-    return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_run_dev: bad argument (need %d <= max_records <= rec_cap)", h->subs_max);
-  const int K = h->K;
-  std::vector<gacq_track_chstate> now(K);
-  GACQ_DEVICE(ctx);
-  hipStream_t stream = ctx->stream;
-  GACQ_HIP(ctx, hipMemcpyAsync(now.data(), h->d_states.p, sizeof(gacq_track_chstate) * K, hipMemcpyDeviceToHost, stream));
-  GACQ_HIP(ctx, hipStreamSynchronize(stream));
-  std::vector<TlRun> runs(K);
-  for (int k = 0; k < K; k++) {
-    if (!d_x[k] || base[k] < 0 || avail[k] < 0)
-      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_run_dev: channel %d: bad samples", k);
-    if (base[k] > now[k].pos)
-      return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_run_dev: channel %d: samples start at %lld, the next block at %lld", k,
-                       base[k], now[k].pos);
-    runs[k].x = (const int8_t*)d_x[k];
-    runs[k].base = base[k];
-    runs[k].end = base[k] + avail[k];
-  }
-  int rc;
-  if ((rc = ensure(ctx, h->d_recs, sizeof(gacq_track_record) * (size_t)K * rec_cap)) != GACQ_OK) return rc;
-  GACQ_HIP(ctx, hipMemcpyAsync(h->d_runs.p, runs.data(), sizeof(TlRun) * K, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(longtrack_kernel, dim3((unsigned)K), dim3(kLtBlock), 0, stream, (const TlSpec*)h->d_specs.p, (const TlRun*)h->d_runs.p,
-                     (gacq_track_chstate*)h->d_states.p, h->d_tab, (gacq_track_record*)h->d_recs.p, rec_cap, max_records);
-  GACQ_HIP(ctx, hipGetLastError());
-  GACQ_HIP(ctx, hipMemcpyAsync(now.data(), h->d_states.p, sizeof(gacq_track_chstate) * K, hipMemcpyDeviceToHost, stream));
-  GACQ_HIP(ctx, hipStreamSynchronize(stream));
-  // only the records written come back: a channel's count is in its state
-  for (int k = 0; k < K; k++) {
-    status[k] = now[k].status;
-    counts[k] = now[k].last_records;
-    if (counts[k] > 0)
-      GACQ_HIP(ctx, hipMemcpyAsync(recs + (size_t)k * rec_cap, (const gacq_track_record*)h->d_recs.p + (size_t)k * rec_cap,
-                                   sizeof(gacq_track_record) * (size_t)counts[k], hipMemcpyDeviceToHost, stream));
-  }
-  GACQ_HIP(ctx, hipStreamSynchronize(stream));
-  return GACQ_OK;
+  return tl_run(h, "gacq_longtrack_run_dev", true, d_x, base, avail, max_records, recs, rec_cap, counts, status, [&](hipStream_t stream) {
+    hipLaunchKernelGGL(longtrack_kernel, dim3((unsigned)h->K), dim3(kLtBlock), 0, stream, (const TlSpec*)h->d_specs.p, (const TlRun*)h->d_runs.p,
+                       (gacq_track_chstate*)h->d_states.p, h->d_tab, (gacq_track_record*)h->d_recs.p, rec_cap, max_records);
+  });
 }
 
-extern "C" int gacq_longtrack_state(gacq_longtrack* h, int k, gacq_track_chstate* out) {
-  if (!h) return GACQ_ERR_BAD_ARG;
-  gacq_ctx* ctx = h->ctx;
-  if (!out || k < 0 || k >= h->K) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_longtrack_state: bad channel %d", k);
-  GACQ_DEVICE(ctx);
-  GACQ_HIP(ctx, hipMemcpyAsync(out, (const gacq_track_chstate*)h->d_states.p + k, sizeof(gacq_track_chstate), hipMemcpyDeviceToHost,
-                               ctx->stream));
-  GACQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return GACQ_OK;
-}
+extern "C" int gacq_longtrack_state(gacq_longtrack* h, int k, gacq_track_chstate* out) { return tl_state(h, "gacq_longtrack_state", k, out); }
 
-extern "C" void gacq_longtrack_close(gacq_longtrack* h) {
-  if (!h) return;
-  {
-    DeviceGuard g(h->ctx->device);
-    (void)hipStreamSynchronize(h->ctx->stream);
-    for (DevBuf* b : {&h->d_specs, &h->d_runs, &h->d_states, &h->d_recs})
-      if (b->p) (void)hipFree(b->p);
-  }
-  delete h;
-}
+extern "C" void gacq_longtrack_close(gacq_longtrack* h) { tl_close(h); }

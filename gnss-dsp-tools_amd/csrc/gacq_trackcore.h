@@ -1,5 +1,6 @@
-// Device helpers shared by the tracking loops (gacq_trackloop.hip: the template scripts; gacq_longtrack.hip: the long-code
-// scripts; gacq_chiptrack.hip: the B2b scripts).  chip_track_kernel (gacq_chiptrack.hip) carries a copy of track_loop_kernel's loop
+// Device helpers and the device-side structs shared by the tracking loops (gacq_trackloop.hip: the template scripts;
+// gacq_longtrack.hip: the long-code scripts; gacq_chiptrack.hip: the B2b scripts).  The host side of their handles -- spec checks,
+// uploads, the bookkeeping around a launch -- is in gacq_trackhost.h, which each file includes after its kernels.  chip_track_kernel (gacq_chiptrack.hip) carries a copy of track_loop_kernel's loop
 // body: a change to one belongs in the other.  Include it after `#pragma clang fp contract(off)`: the helpers round every product and sum on their own, as the
 // reference does, and only the phases written as fma() are fused.
 #pragma once

@@ -114,18 +114,12 @@ static int correlate_run(gacq_ctx* ctx, const float* x_iq, const float2* d_xdev,
     ctx->tr_code.clear();
     ctx->tr_chips.assign(K, nullptr);
     for (int k = 0; k < K; k++) {
-      const std::string key = std::string("chips:") + code + ":" + std::to_string(prns[k]);
-      const void* dchips = nullptr;
-      auto it = ctx->tables.find(key);
-      if (it == ctx->tables.end()) {
-        std::vector<uint8_t> h(len);
-        const int rc = gacq_code_chips(code, prns[k], h.data(), len);
-        if (rc < 0) return set_error(ctx, rc, "gacq_correlate_batch: no PRN %d in '%s'", prns[k], code);
-        const int rc2 = table_cache(ctx, key, h.data(), (size_t)len, &dchips);
-        if (rc2 != GACQ_OK) return rc2;
-      } else {
-        dchips = it->second.p;
-      }
+      ChipTable t;
+      const uint8_t* dchips = nullptr;
+      const int rc = chip_table_host(ctx, code, prns[k], len, true, t);
+      if (rc < 0) return set_error(ctx, rc, "gacq_correlate_batch: no PRN %d in '%s'", prns[k], code);
+      const int rc2 = chip_table_dev(ctx, t, &dchips);
+      if (rc2 != GACQ_OK) return rc2;
       ctx->tr_chips[k] = dchips;
     }
     ctx->tr_prns.assign(prns, prns + K);

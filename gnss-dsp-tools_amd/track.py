@@ -10,21 +10,22 @@ Output: the script's lines ('%d %f ...', 9 or 14 columns), one per track() call,
 import optparse
 import sys
 
-from . import chiptrack, longtrack, trackloop
+from . import longtrack, trackloop
 
-
-def _tracker(name):
-    return trackloop.TRACKERS[name] if name in trackloop.TRACKERS else longtrack.LONG_TRACKERS[name]
+TRACKERS = {**trackloop.TRACKERS, **longtrack.LONG_TRACKERS}
 
 
 def names():
     """Every tracker name the command line accepts."""
-    return sorted(list(trackloop.TRACKERS) + list(longtrack.LONG_TRACKERS))
+    return sorted(TRACKERS)
 
 
-def build_parser(name):
-    p = optparse.OptionParser(usage="%s [options] input_filename sample_rate carrier_offset %s doppler code_offset"
-                              % (name, "chan" if _tracker(name).glonass else "PRN"))
+def _usage(name, trackers):
+    return "input_filename sample_rate carrier_offset %s doppler code_offset" % ("chan" if trackers[name].glonass else "PRN")
+
+
+def build_parser(name, trackers=TRACKERS):
+    p = optparse.OptionParser(usage="%s [options] %s" % (name, _usage(name, trackers)))
     p.disable_interspersed_args()
     p.add_option("--loop-dwells", default="500,500", help="initial time intervals for wide FLL, then narrow FLL, in milliseconds "
                                                           "(default %default)")
@@ -32,13 +33,13 @@ def build_parser(name):
     return p
 
 
-def parse(name, argv):
-    """Channel of one command line (argv after the tracker name), with the script's own argument conversions."""
-    if name not in trackloop.TRACKERS and name not in longtrack.LONG_TRACKERS:
-        raise SystemExit("unknown tracker %r; the trackers: %s" % (name, " ".join(names())))
-    options, args = build_parser(name).parse_args(list(argv))
+def parse(name, argv, trackers=TRACKERS, what="tracker"):
+    """(path, Channel) of one command line (argv after the tracker name), with the script's own argument conversions."""
+    if name not in trackers:
+        raise SystemExit("unknown %s %r; the %ss: %s" % (what, name, what, " ".join(sorted(trackers))))
+    options, args = build_parser(name, trackers).parse_args(list(argv))
     if len(args) < 6:
-        raise SystemExit("%s: need input_filename sample_rate carrier_offset %s doppler code_offset" % (name, "chan" if _tracker(name).glonass else "PRN"))
+        raise SystemExit("%s: need %s" % (name, _usage(name, trackers)))
     dwells = tuple(map(float, options.loop_dwells.split(",")))        # util.parse_list_floats
     phase = float(options.carrier_phase) if options.carrier_phase is not None else None
     ch = trackloop.Channel(name, float(args[1]), float(args[2]), int(args[3]), float(args[4]), float(args[5]), dwells, phase)
@@ -55,6 +56,7 @@ def run(name, argv, out=sys.stdout):
 
 
 def main(argv=None):
+    from . import chiptrack            # it imports this module for the parser
     argv = sys.argv[1:] if argv is None else argv
     if not argv or argv[0] in ("-h", "--help"):
         sys.stdout.write(__doc__ + "\ntrackers: " + " ".join(names() + sorted(chiptrack.CHIP_TRACKERS)) + "\n")

@@ -108,11 +108,12 @@ class Channel:
     carrier_phase: float = None
 
 
-def channel_spec(ch):
-    """gacq_track_spec of a channel, with the script's own arithmetic for everything derived from its arguments."""
-    if ch.name not in TRACKERS:
-        raise KeyError("unknown tracker %r (the template family: %s)" % (ch.name, ", ".join(sorted(TRACKERS))))
-    t = TRACKERS[ch.name]
+def channel_spec(ch, trackers=TRACKERS):
+    """gacq_track_spec of a channel, with the script's own arithmetic for everything derived from its arguments.  ``trackers``: the
+    table that holds the channel's name (longtrack.LONG_TRACKERS and chiptrack.CHIP_TRACKERS go through their own wrappers)."""
+    if ch.name not in trackers:
+        raise KeyError("unknown tracker %r (the template family: %s)" % (ch.name, ", ".join(sorted(trackers))))
+    t = trackers[ch.name]
     fs, coffset = float(ch.fs), float(ch.coffset)
     wide, narrow = (float(ch.loop_dwells[0]), float(ch.loop_dwells[1]))
     phase = 0.0
@@ -157,7 +158,12 @@ class TrackLoop:
         self.records = [[] for _ in range(self.K)]
         self.status = [0] * self.K
 
-    # what a subclass with its own tracker table and C entry points overrides (chiptrack.ChipTrackLoop)
+    # what a subclass with its own tracker table and C entry points overrides (longtrack.LongTrackLoop, chiptrack.ChipTrackLoop)
+    _lib = "gacq_track"                    # the entry points are <_lib>_open, _run_dev, _state and _close
+
+    def _call(self, what, *args):
+        return getattr(nat.lib, "%s_%s" % (self._lib, what))(*args)
+
     @staticmethod
     def _trackers():
         return TRACKERS
@@ -168,12 +174,12 @@ class TrackLoop:
 
     def _open(self):
         h = ctypes.c_void_p()
-        nat.check(nat.lib.gacq_track_open(self.eng._ctx, self._specs, self.K, ctypes.byref(h)), self.eng._ctx)
+        nat.check(self._call("open", self.eng._ctx, self._specs, self.K, ctypes.byref(h)), self.eng._ctx)
         return h
 
     def close(self):
         if self._h:
-            nat.lib.gacq_track_close(self._h)
+            self._call("close", self._h)
             self._h = None
 
     def __del__(self):
@@ -184,11 +190,8 @@ class TrackLoop:
 
     def state(self, k):
         out = np.zeros(1, dtype=STATE_DTYPE)
-        nat.check(nat.lib.gacq_track_state(self._h, k, out.ctypes.data_as(ctypes.c_void_p)), self.eng._ctx)
+        nat.check(self._call("state", self._h, k, out.ctypes.data_as(ctypes.c_void_p)), self.eng._ctx)
         return out[0]
-
-    def _run_dev(self, ptrs, base, avail, recs, cap, counts, status):
-        return nat.lib.gacq_track_run_dev(self._h, ptrs, base, avail, self.max_records, recs, cap, counts, status)
 
     def _launch(self, xs, bases):
         torch = nat.require_torch()
@@ -213,9 +216,9 @@ class TrackLoop:
         recs = np.zeros((self.K, cap), dtype=RECORD_DTYPE)
         counts = np.zeros(self.K, dtype=np.int32)
         status = np.zeros(self.K, dtype=np.int32)
-        nat.check(self._run_dev(ptrs, base.ctypes.data_as(ctypes.c_void_p), avail.ctypes.data_as(ctypes.c_void_p),
-                                recs.ctypes.data_as(ctypes.c_void_p), cap, counts.ctypes.data_as(nat.c_int_p),
-                                status.ctypes.data_as(nat.c_int_p)), self.eng._ctx)
+        nat.check(self._call("run_dev", self._h, ptrs, base.ctypes.data_as(ctypes.c_void_p), avail.ctypes.data_as(ctypes.c_void_p),
+                             self.max_records, recs.ctypes.data_as(ctypes.c_void_p), cap, counts.ctypes.data_as(nat.c_int_p),
+                             status.ctypes.data_as(nat.c_int_p)), self.eng._ctx)
         del keep
         out = [recs[k, :counts[k]].copy() for k in range(self.K)]
         for k in range(self.K):
@@ -268,9 +271,9 @@ class TrackLoop:
         return [np.concatenate(n) for n in new]
 
 
-def format_lines(name, recs, chip_rate=None):
-    """The script's output lines ('%d %f ...' with 9 or 14 columns) from a record array."""
-    t = TRACKERS[name]
+def format_lines(name, recs, chip_rate=None, trackers=TRACKERS):
+    """The script's output lines ('%d %f ...' with the 9 or 14 columns of the tracker's entry) from a record array."""
+    t = trackers[name]
     cr = float(codes.chip_rate(t.code) if chip_rate is None else chip_rate)
     out = []
     for r in recs:
@@ -293,13 +296,16 @@ def load_int8(path, device=0):
     return torch.from_numpy(raw).to("cuda:%d" % device)
 
 
-def track_file(name, path, fs, coffset, prn, doppler, code_offset, loop_dwells=(500.0, 500.0), carrier_phase=None, engine=None):
-    """One script run on one file: returns (records, output lines)."""
+def track_file(name, path, fs, coffset, prn, doppler, code_offset, loop_dwells=(500.0, 500.0), carrier_phase=None, engine=None,
+               loop=TrackLoop, **loop_args):
+    """One script run on one file with the loop class of the script's family: returns (records, output lines), and the chip
+    accumulator as well from a loop that has one."""
     ch = Channel(name, fs, coffset, prn, doppler, code_offset, tuple(loop_dwells), carrier_phase)
     eng = engine or acquire.default_engine()
-    tl = TrackLoop([ch], eng)
+    tl = loop([ch], eng, **loop_args)
     try:
         recs = tl.run([load_int8(path, eng.device)])[0]
+        more = (tl.chips(0),) if hasattr(tl, "chips") else ()
     finally:
         tl.close()
-    return recs, format_lines(name, recs)
+    return (recs, format_lines(name, recs, trackers=tl._trackers())) + more
