@@ -88,6 +88,9 @@ struct gacq_ctx {
   gacq::DevBuf pin_fold[2];            // gacq_fold_dev: pinned staging of the parameter block, two slots in turn
   hipEvent_t fold_done[2] = {nullptr, nullptr};   // ... and the event after the launch that last used each slot
   int fold_slot = 0;
+  gacq::DevBuf pin_sim[2];             // gacq_simulate_dev: the same two-slot staging for its parameter block (satellites, symbol bits)
+  hipEvent_t sim_done[2] = {nullptr, nullptr};
+  int sim_slot = 0;
   gacq::DevBuf pin_tie;                // pinned host word the listing kernels set when the re-evaluation list is full (GACQ_WARN_TIE_LIST_FULL)
   gacq::DevBuf bar_x;                  // fine-grained device memory the host writes directly through the PCIe BAR (small gacq_search inputs)
   gacq::DevBuf bar_s;                  // the same for the correlator specs of gacq_correlate_batch_dev

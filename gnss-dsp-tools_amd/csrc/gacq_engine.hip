@@ -563,6 +563,8 @@ void gacq_destroy(gacq_ctx* ctx) {
   for (int k = 0; k < 2; k++) {
     if (ctx->pin_fold[k].p) (void)hipHostFree(ctx->pin_fold[k].p);
     if (ctx->fold_done[k]) (void)hipEventDestroy(ctx->fold_done[k]);
+    if (ctx->pin_sim[k].p) (void)hipHostFree(ctx->pin_sim[k].p);
+    if (ctx->sim_done[k]) (void)hipEventDestroy(ctx->sim_done[k]);
   }
   if (ctx->bar_x.p) (void)hipFree(ctx->bar_x.p);
   if (ctx->bar_s.p) (void)hipFree(ctx->bar_s.p);

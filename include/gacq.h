@@ -527,6 +527,46 @@ int gacq_corr_grid_dev(gacq_ctx* ctx, const gacq_grid_spec* specs, int K, const 
 int gacq_fold_dev(gacq_ctx* ctx, const void* d_x, int wide, long long avail, int n_out, int M, int D, int H, const long long* start,
                   const double* f_d, double fs, long long j0, const signed char* W, void* d_y);
 
+/* ---------------------------------------------------------------------------------------------
+ * Synthetic recordings (gacq_simulate.hip): samples j = j0 .. j0 + n - 1 of one endless recording of K satellites plus white noise,
+ * an exact function of (scene, seed, absolute sample index j) -- the same bytes however a caller cuts it into calls:
+ *     v(j) = noise(j) + sum_{k<K} amp_k w_k(j) d_k(j) exp(2 pi i theta_k(j) / 2^64),       noise first, then k ascending, in fp32.
+ * Per satellite, converted once from the doubles below in IEEE double operations:
+ *     F = floor(frac(carrier_hz / fs) 2^64), p0 likewise from carrier_phase (turns); theta(j) = (p0 + j F) mod 2^64.  The frequency
+ *       produced differs from the request by less than fs 2^-53.
+ *     Cf = floor((code_rate_hz / fs) 2^64), c0 likewise from code_phase (chips at j = 0); pos(j) = c0 + j Cf, an exact integer:
+ *       chip index (pos >> 64) mod L, period (pos >> 64) div L, subchip fraction pos mod 2^64.
+ *     w: the chip weight of correlator kind 0..5 (plain, BOC(1,1), CBOC 0.953463 / 0.301511, TMBOC, RZ [1,0], RZ [0,1]) with the
+ *       half-chip bit = top bit of the fraction and the BOC(6,1) bit = floor(12 fraction / 2^64) mod 2.
+ *     d = symbols[(period div periods_per_symbol) mod nsym], +1 when nsym = 0.
+ * noise: Philox4x32-10, key (seed lo32, seed hi32), counter (j lo32, j hi32, 0, 0), words r0, r1;
+ *     u1 = ((r0 >> 8) + 0.5) 2^-24, u2 = ((r1 >> 8) + 0.5) 2^-24, (nI, nQ) = sigma sqrt(-2 ln u1) (cos 2 pi u2, sin 2 pi u2).
+ * d_out (device): complex64 [n] (out_complex64 != 0, 8-byte aligned), or interleaved signed 8-bit I/Q [2 n] = clip(rint(v), -127, 127)
+ * with ties to even, of the very values the complex64 form holds.
+ * Every argument is checked before anything is allocated or launched: K outside 1..32, n < 1, j0 < 0, j0 + n > 2^48, a value that is
+ * not finite, fs <= 0, sigma < 0, code_rate_hz <= 0 or code_rate_hz / fs >= 16, code_phase outside [0, L), kind outside 0..5, nsym < 0
+ * or > 2^20, a symbol other than +-1, periods_per_symbol < 1, a NULL pointer GACQ_ERR_BAD_ARG; an unknown code or PRN
+ * GACQ_ERR_UNKNOWN_CODE / GACQ_ERR_BAD_PRN.  Chip tables are the context's cached ones (shared with the tracking loops), generated on
+ * first use.  One launch on the ctx stream, no state kept; asynchronous.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gacq_sim_sat {
+  const char* code;                /* code module, e.g. "gps.ca" */
+  int prn;                         /* PRN (GLONASS: 0) */
+  int kind;                        /* chip weight, 0 plain .. 5 RZ [0,1] */
+  int periods_per_symbol;          /* code periods per symbol, >= 1 */
+  int nsym;                        /* symbols, 0..2^20; 0: every symbol is +1 */
+  int pad;
+  const int8_t* symbols;           /* nsym values +-1 (host memory); may be NULL when nsym = 0 */
+  double amp;                      /* amplitude per component, LSB */
+  double carrier_hz;               /* carrier frequency in the recording, Hz (offset + Doppler) */
+  double carrier_phase;            /* carrier phase at j = 0, turns */
+  double code_rate_hz;             /* chips per second */
+  double code_phase;               /* code phase at j = 0, chips, in [0, L) */
+} gacq_sim_sat;
+
+int gacq_simulate_dev(gacq_ctx* ctx, const gacq_sim_sat* sats, int K, double fs, double sigma, unsigned long long seed, long long j0,
+                      long long n, int out_complex64, void* d_out);
+
 /* Per-stage GPU time from HIP events recorded on the launch stream (profiling aid for bench.py).
  * Stages: 0 mix/forward, 1 forward FFT (rocFFT), 2 conj-multiply, 3 inverse FFT (rocFFT),
  *         4 magnitude/peak reduce, 5 best-over-Doppler, 6 fused correlate kernel (LDS FFT). */
