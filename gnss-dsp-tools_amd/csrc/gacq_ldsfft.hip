@@ -868,6 +868,9 @@ __global__ __launch_bounds__(kBlock, MINW) void lds_correlate_kernel(const float
 #ifndef GACQ_PRE4K
 #define GACQ_PRE4K 13     // batch kernel: pass-1 powers in registers (1) + pass-2 powers from the LDS table (4) + rising wave priorities (8)
 #endif
+#ifndef GACQ_F4K_RING
+#define GACQ_F4K_RING 32  // item loop of the fused kernel: rows between two combines of the per-wave partials (1 = after every row, A/B only)
+#endif
 
 // ---- N = 4096, one block, one carrier: forward + correlate in ONE kernel ---------------------------------------------------
 // Workgroup = (epoch, Doppler bin, chunk of pch items).  Prologue: load the x window, table-NCO mix (fp64 index as in
@@ -880,6 +883,15 @@ __global__ __launch_bounds__(kBlock, MINW) void lds_correlate_kernel(const float
 // lds_forward_kernel + lds_correlate_kernel: records are bit-identical (test_fused_4096_kernel_equals_two_kernel_path).
 // PREA: keep the 15 pass-1 twiddle powers of the inverse transform in registers for the whole item loop (30 VGPRs, 14 complex
 // products per row less); the maximum-first peak search freed exactly that much of the 128-register budget of 4 waves per SIMD.
+// Records (GACQ_F4K_RING): lane 0 of each wave writes its partial (peak, idx | tie bit, sum) of item p into slot (p - p0) & 31 of a
+// 32 x 4 ring in LDS before the row's closing barrier.  After the barrier of slot 31, or of the chunk's last row, lane s <= slot of
+// wave 0 combines the four partials of item p - slot + s (combine_tagged over waves 0..3, sum ((s0 + s1) + s2) + s3 in fp64: the
+// values and the order of a combine after every row, so the records are the same bits) and stores its record.  The combine -- four
+// dependent LDS round trips, ~45 instructions, three fp64 adds, the record store -- used to run on one lane after every row while
+// the other three waves waited for wave 0 at the next row's first barrier; now once per 32 rows, 32 lanes wide.  The ring is safe
+// for any pch: wave 0 flushes before it reaches that barrier and no wave writes a slot again before the same row's third one.
+// Fetching the next item's code row ahead (behind the magnitudes, in flight across the closing barrier) measured 3 % SLOWER on its
+// own and no faster on top of the ring (profiles/r14_fused4k_item_loop_ab.log): not built in.
 // (Round 3's single-launch instantiation -- the Doppler scan by the workgroup that completes an item's last bin, records handed
 // over with agent-scope stores and an arrival counter -- measured slower than the three short launches it replaced (21.8 us of kernel
 // against 6.8 + 12.3 + 6.5 us whose launch latencies overlap, profiles/r03_single_search_latency.log) and had no hook for the tie-safe
@@ -890,10 +902,12 @@ __global__ __launch_bounds__(kBlock, MINW) void lds_fused4k_kernel(const float2*
                                                                     const double* __restrict__ freq, const float2* __restrict__ nco_tab,
                                                                     const float2* __restrict__ tw, RowRec* __restrict__ rows, int E, int P,
                                                                     int D, int pch, int nchunk, int by_epoch, float tie_scale) {
+  constexpr int kRing = GACQ_F4K_RING;                // item slots between two flushes: a power of two, at most 64 (one lane each)
+  static_assert(kRing >= 1 && kRing <= 64 && (kRing & (kRing - 1)) == 0, "GACQ_F4K_RING");
   __shared__ v2 lds[kLdsElems];
-  __shared__ float s_peak[kBlock / 64];
-  __shared__ int s_idx[kBlock / 64];
-  __shared__ double s_sum[kBlock / 64];
+  __shared__ float s_rpeak[kRing][kBlock / 64];
+  __shared__ int s_ridx[kRing][kBlock / 64];
+  __shared__ float s_rsum[kRing][kBlock / 64];
   const int t = threadIdx.x;
   // Placement (workgroup b runs on XCD b % 8).  Batches: all D x nchunk workgroups of an epoch go to XCD e % 8, so the epoch's
   // sample block is fetched into one L2 instead of eight (round 2: 8.3 x the compulsory fetch).  Few epochs: (epoch, Doppler)
@@ -977,13 +991,14 @@ __global__ __launch_bounds__(kBlock, MINW) void lds_fused4k_kernel(const float2*
     wave_first_max(m, (unsigned)__builtin_amdgcn_readfirstlane(t & ~63), 1u, 256u, tie_scale, wmaxf, widx);
     const unsigned wmax = __builtin_bit_cast(unsigned, wmaxf * inv_n);
     const float wsum = wave_add_f32(sum_f * inv_n);
-    if ((t & 63) == 0) { s_peak[t >> 6] = __builtin_bit_cast(float, wmax); s_idx[t >> 6] = (int)widx; s_sum[t >> 6] = (double)wsum; }
-    __syncthreads();   // also orders this item's exchange-2 reads before the next item's exchange-1 writes
-    if (t == 0) {
+    const int slot = (p - p0) & (kRing - 1);
+    if ((t & 63) == 0) { s_rpeak[slot][t >> 6] = __builtin_bit_cast(float, wmax); s_ridx[slot][t >> 6] = (int)widx; s_rsum[slot][t >> 6] = wsum; }
+    lds_barrier();     // also orders this item's exchange-2 reads before the next item's exchange-1 writes
+    if ((slot == kRing - 1 || p == p1 - 1) && t <= slot) {
       RowRec r;
-      combine_tagged(kBlock / 64, [&](int w) { return s_peak[w]; }, [&](int w) { return s_idx[w]; }, tie_scale, r.peak, r.idx);
-      r.sum = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
-      rows[(e * P + p) * (long)D + d] = r;
+      combine_tagged(kBlock / 64, [&](int w) { return s_rpeak[t][w]; }, [&](int w) { return s_ridx[t][w]; }, tie_scale, r.peak, r.idx);
+      r.sum = (((double)s_rsum[t][0] + (double)s_rsum[t][1]) + (double)s_rsum[t][2]) + (double)s_rsum[t][3];
+      rows[(e * P + (p - slot + t)) * (long)D + d] = r;
     }
   }
 }
