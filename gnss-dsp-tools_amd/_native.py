@@ -215,6 +215,13 @@ SYMBOLS = {
     "gacq_debug_fft_plans": (ctypes.c_int, [ctypes.c_void_p]),
     "gacq_acquire_int8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_double, c_double_p, ctypes.c_int,
                                          ctypes.c_size_t, c_int_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_void_p]),
+    # many windows of one recording (scan.py): the window starts as a plain host address (int64)
+    "gacq_frontend_batch_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t,
+                                               ctypes.c_double, ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t,
+                                               ctypes.c_void_p]),
+    "gacq_scan_int8_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t,
+                                          ctypes.c_double, ctypes.c_double, c_double_p, ctypes.c_int, ctypes.c_size_t, c_int_p, ctypes.c_int,
+                                          c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_void_p]),
     "gacq_debug_row": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double,
                                       ctypes.c_double, ctypes.c_int, c_float_p]),
 }

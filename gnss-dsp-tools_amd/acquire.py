@@ -485,9 +485,10 @@ class Engine:
         return _as_tuples(res)
 
     # -- front-end on the GPU (acquire-gps-l1.py:87-96) ---------------------------------------------------
-    def frontend_dev(self, name, iq_int8, fs, coffset, ms_pad):
+    def frontend_dev(self, name, iq_int8, fs, coffset, ms_pad, ntaps=161):
         """iq_int8: numpy int8 array [n, 2] (or flat interleaved) or a torch int8 CUDA tensor; returns a torch complex64
-        CUDA tensor with ms_pad ms of samples at the signal's internal rate, ready for search_batch_dev."""
+        CUDA tensor with ms_pad ms of samples at the signal's internal rate, ready for search_batch_dev.  ntaps: length of the
+        Hann low-pass (the reference's scripts all use 161)."""
         torch = nat.require_torch()
         sig = _signals.get(name) if isinstance(name, str) else name
         if not torch.is_tensor(iq_int8):
@@ -497,11 +498,60 @@ class Engine:
         n_in = iq_int8.numel() // 2
         per_ms = int(round(sig.fs * 0.001))
         n_out = int(ms_pad) * per_ms
-        taps = firwin_hann(161, sig.fir_cutoff / (fs / 2))
+        taps = firwin_hann(ntaps, sig.fir_cutoff / (fs / 2))
         out = torch.empty(n_out, dtype=torch.complex64, device=iq_int8.device)
         nat.check(nat.lib.gacq_frontend_dev(self._ctx, ctypes.c_void_p(iq_int8.data_ptr()), n_in, float(fs), float(coffset),
                                             taps.ctypes.data_as(nat.c_double_p), len(taps), sig.fs, n_out,
                                             ctypes.c_void_p(out.data_ptr())), self._ctx)
+        return out
+
+    # -- many windows of one recording (scan.py) -------------------------------------------------------------
+    def frontend_batch_dev(self, name, iq_int8, starts, n_in, fs, coffset, ms_pad, ntaps=161, out=None):
+        """gacq_frontend_batch_dev: iq_int8 = the recording as a flat interleaved torch int8 CUDA tensor, starts = first sample of
+        every window (n_in samples each, any overlap).  Returns a torch complex64 CUDA tensor [len(starts), ms_pad ms at the signal's
+        rate] whose row w holds the bits frontend_dev returns for iq_int8[2*starts[w] : 2*(starts[w] + n_in)]."""
+        torch = nat.require_torch()
+        sig = _signals.get(name) if isinstance(name, str) else name
+        if not (torch.is_tensor(iq_int8) and iq_int8.is_cuda and iq_int8.dtype == torch.int8 and iq_int8.dim() == 1 and iq_int8.is_contiguous()):
+            raise ValueError("iq_int8 must be a flat, contiguous int8 CUDA tensor")
+        self.use_torch_stream(iq_int8.device)
+        starts = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
+        n_out = int(ms_pad) * int(round(sig.fs * 0.001))
+        taps = firwin_hann(ntaps, sig.fir_cutoff / (fs / 2))
+        if out is None:
+            out = torch.empty((len(starts), n_out), dtype=torch.complex64, device=iq_int8.device)
+        elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.complex64 and tuple(out.shape) == (len(starts), n_out) and out.is_contiguous()):
+            raise ValueError("out must be a contiguous complex64 CUDA tensor of shape (%d, %d)" % (len(starts), n_out))
+        nat.check(nat.lib.gacq_frontend_batch_dev(self._ctx, ctypes.c_void_p(iq_int8.data_ptr()), iq_int8.numel() // 2, starts.ctypes.data,
+                                                  len(starts), int(n_in), float(fs), float(coffset), taps.ctypes.data_as(nat.c_double_p),
+                                                  len(taps), sig.fs, n_out, ctypes.c_void_p(out.data_ptr())), self._ctx)
+        return out
+
+    def scan_int8_dev(self, name, iq_int8, starts, n_in, fs, coffset, ms_pad, items, dopplers, blocks, out=None):
+        """gacq_scan_int8_dev: batched front-end, then one batched search with the windows as its epochs.  Returns (or fills `out`
+        with) the gacq_peak records as search_batch_dev does: float64 [len(starts), len(items), 2], on the device or in pinned host
+        memory.  Asynchronous on the engine's stream."""
+        torch = nat.require_torch()
+        sig = _signals.get(name) if isinstance(name, str) else name
+        if not (torch.is_tensor(iq_int8) and iq_int8.is_cuda and iq_int8.dtype == torch.int8 and iq_int8.dim() == 1 and iq_int8.is_contiguous()):
+            raise ValueError("iq_int8 must be a flat, contiguous int8 CUDA tensor")
+        self.use_torch_stream(iq_int8.device)
+        starts = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
+        s, idx, bias = self._plan(sig, items)
+        dopplers = np.ascontiguousarray(dopplers, dtype=np.float64)
+        shape = (len(starts), len(idx), 2)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=iq_int8.device)
+        elif not (torch.is_tensor(out) and out.dtype == torch.float64 and tuple(out.shape) == shape and out.is_contiguous()
+                  and (out.is_cuda or out.is_pinned())):
+            raise ValueError("out must be a contiguous float64 tensor of shape %r on the device (or pinned host memory)" % (shape,))
+        n_out = int(ms_pad) * int(round(sig.fs * 0.001))
+        taps = firwin_hann(161, sig.fir_cutoff / (fs / 2))
+        nat.check(nat.lib.gacq_scan_int8_dev(
+            s._h, ctypes.c_void_p(iq_int8.data_ptr()), iq_int8.numel() // 2, starts.ctypes.data, len(starts), int(n_in), float(fs), float(coffset),
+            taps.ctypes.data_as(nat.c_double_p), len(taps), n_out, idx.ctypes.data_as(nat.c_int_p), len(idx),
+            dopplers.ctypes.data_as(nat.c_double_p) if len(dopplers) else None, len(dopplers),
+            bias.ctypes.data_as(nat.c_double_p) if bias is not None else None, max(int(blocks), 0), ctypes.c_void_p(out.data_ptr())), self._ctx)
         return out
 
     def mix_int8_dev(self, iq_int8, fs, coffset):

@@ -91,6 +91,9 @@ struct gacq_ctx {
   gacq::DevBuf pin_sim[2];             // gacq_simulate_dev: the same two-slot staging for its parameter block (satellites, symbol bits)
   hipEvent_t sim_done[2] = {nullptr, nullptr};
   int sim_slot = 0;
+  gacq::DevBuf pin_scan[2];            // gacq_frontend_batch_dev: the same two-slot staging for the window starts
+  hipEvent_t scan_done[2] = {nullptr, nullptr};
+  int scan_slot = 0;
   gacq::DevBuf pin_tie;                // pinned host word the listing kernels set when the re-evaluation list is full (GACQ_WARN_TIE_LIST_FULL)
   gacq::DevBuf bar_x;                  // fine-grained device memory the host writes directly through the PCIe BAR (small gacq_search inputs)
   gacq::DevBuf bar_s;                  // the same for the correlator specs of gacq_correlate_batch_dev
@@ -255,6 +258,13 @@ int split_debug_nco(gacq_ctx* ctx, int N, int n, const double* d_freq, int* d_id
 
 // front-end carrier wipe-off alone (gacq_frontend.hip): int8 I/Q on the device -> complex64, fixed-point table NCO
 int frontend_mix(gacq_ctx* ctx, const void* d_iq_int8, long n, double fs_in, double carrier_offset_hz, float2* d_out);
+// the pieces of gacq_frontend_dev that the batched front-end (gacq_scan.hip) shares: the mixer's phase step, floor(f*NT*2^50) for
+// f = -offset/fs, and the upload of the filter, rounded to fp32, into ctx->fe_taps (skipped when the last call used the same taps)
+long long frontend_mix_step(double fs_in, double carrier_offset_hz);
+int frontend_taps(gacq_ctx* ctx, const double* taps, int ntaps);
+// the refusals of gacq_frontend_batch_dev (gacq_scan.hip), for callers that must make them before work of their own is queued
+int frontend_batch_check(gacq_ctx* ctx, const void* d_iq_int8, long long nsamp_avail, const long long* starts, int nwin, size_t nsamp_in,
+                         double fs_in, double carrier_offset_hz, const double* taps, int ntaps, double fs_out, size_t nsamp_out, const void* d_out);
 
 // split engines (gacq_split.hip): N = R*M, hand-written outer DFT-R, inner length-M transforms (rocFFT or the 4096 kernels)
 bool split_supported(int N);

@@ -565,6 +565,8 @@ void gacq_destroy(gacq_ctx* ctx) {
     if (ctx->fold_done[k]) (void)hipEventDestroy(ctx->fold_done[k]);
     if (ctx->pin_sim[k].p) (void)hipHostFree(ctx->pin_sim[k].p);
     if (ctx->sim_done[k]) (void)hipEventDestroy(ctx->sim_done[k]);
+    if (ctx->pin_scan[k].p) (void)hipHostFree(ctx->pin_scan[k].p);
+    if (ctx->scan_done[k]) (void)hipEventDestroy(ctx->scan_done[k]);
   }
   if (ctx->bar_x.p) (void)hipFree(ctx->bar_x.p);
   if (ctx->bar_s.p) (void)hipFree(ctx->bar_s.p);
@@ -1476,6 +1478,36 @@ int gacq_acquire_int8(gacq_sig* sig, const int8_t* iq_int8, size_t nsamp_in, dou
   GACQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
   rc = gacq_finalize(&sig->desc, (const gacq_peak*)ctx->pin_peaks.p, 1, nullptr, nitems, dopplers, nd, out);
   return rc != GACQ_OK ? rc : tie_list_full_warning(ctx);
+}
+
+// gacq_acquire_int8 for many windows of a recording that is already on the device: the batched front-end writes the windows of a chunk
+// into acq_x, one batched search reads them as its epochs.  A chunk is what the workspace budget allows acq_x (the front-end cuts it
+// further if its own intermediates need that).  Asynchronous.
+int gacq_scan_int8_dev(gacq_sig* sig, const void* d_iq_int8, long long nsamp_avail, const long long* starts, int nwin, size_t nsamp_in,
+                       double fs_in, double carrier_offset_hz, const double* taps, int ntaps, size_t nsamp_out, const int* items, int nitems,
+                       const double* dopplers, int nd, const double* item_bias_hz, int blocks, void* d_peaks) {
+  if (!sig || !d_iq_int8 || !taps || nsamp_in == 0 || nsamp_out == 0 || !(fs_in > 0.0) || !std::isfinite(carrier_offset_hz))
+    return set_error(sig ? sig->ctx : nullptr, GACQ_ERR_BAD_ARG, "gacq_scan_int8_dev: bad argument");
+  gacq_ctx* ctx = sig->ctx;
+  // the search's checks against the front-end's output length, then the front-end's own: all of them before anything is launched
+  static const float dummy = 0.f;
+  int rc = check_search_args(sig, &dummy, nsamp_out, nwin, items, nitems, dopplers, nd, blocks, d_peaks);
+  if (rc != GACQ_OK) return rc;
+  rc = frontend_batch_check(ctx, d_iq_int8, nsamp_avail, starts, nwin, nsamp_in, fs_in, carrier_offset_hz, taps, ntaps, sig->desc.fs, nsamp_out, &dummy);
+  if (rc != GACQ_OK) return rc;
+  GACQ_DEVICE(ctx);
+  const int Wc = (int)std::max<size_t>(1, std::min<size_t>((size_t)nwin, ws_budget(ctx) / (sizeof(float2) * nsamp_out)));
+  if ((rc = ensure(ctx, ctx->acq_x, sizeof(float2) * nsamp_out * (size_t)Wc)) != GACQ_OK) return rc;
+  for (int w0 = 0; w0 < nwin; w0 += Wc) {
+    const int W = std::min(Wc, nwin - w0);
+    rc = gacq_frontend_batch_dev(ctx, d_iq_int8, nsamp_avail, starts + w0, W, nsamp_in, fs_in, carrier_offset_hz, taps, ntaps, sig->desc.fs, nsamp_out,
+                                 ctx->acq_x.p);
+    if (rc != GACQ_OK) return rc;
+    rc = gacq_search_batch_dev(sig, ctx->acq_x.p, nsamp_out, W, items, nitems, dopplers, nd, item_bias_hz, blocks,
+                               (gacq_peak*)d_peaks + (size_t)w0 * nitems);
+    if (rc != GACQ_OK) return rc;
+  }
+  return GACQ_OK;
 }
 
 int gacq_debug_fft_plans(gacq_ctx* ctx) {

@@ -319,6 +319,31 @@ int gacq_acquire_int8(gacq_sig* sig, const int8_t* iq_int8, size_t nsamp_in, dou
                       int ntaps, size_t nsamp_out, const int* items, int nitems, const double* dopplers, int nd,
                       const double* item_bias_hz, int blocks, gacq_result* out);
 
+/* The front-end for many windows of one recording at once: window w is the nsamp_in samples that begin at sample starts[w] of
+ * d_iq_int8 (interleaved signed 8-bit I/Q on the device, nsamp_avail complex samples; any start is allowed, windows may overlap or
+ * leave gaps), and row w of d_out (complex64 [nwin][nsamp_out]) is, bit for bit, what gacq_frontend_dev writes for that slice: the
+ * mixer phase restarts at 0 and filtfilt extends every window on its own.  One launch set serves all windows of a chunk; a chunk is
+ * as many windows as the workspace limit allows intermediates, and the result does not depend on the chunking.  For the 161-tap
+ * filter the backward pass and the resampler are one kernel that computes only the two filtered samples each output reads.
+ * starts: HOST array, int64, staged by the call (it may be reused on return).  GACQ_ERR_SHORT_INPUT when nsamp_in <= 3*ntaps or a
+ * window does not lie inside [0, nsamp_avail); refusals are made before anything is allocated or launched.  Asynchronous. */
+int gacq_frontend_batch_dev(gacq_ctx* ctx, const void* d_iq_int8, long long nsamp_avail, const long long* starts, int nwin,
+                            size_t nsamp_in, double fs_in, double carrier_offset_hz, const double* taps, int ntaps, double fs_out,
+                            size_t nsamp_out, void* d_out);
+
+/* gacq_acquire_int8 at many positions of a recording that is already on the device (scan.py): gacq_frontend_batch_dev into a
+ * library-owned buffer, then ONE gacq_search_batch_dev with the windows as its epochs, per chunk of windows that fits the workspace
+ * limit.  d_peaks: gacq_peak [nwin][nitems], device or device-visible pinned memory; gacq_finalize turns a row into the results
+ * gacq_acquire_int8 returns for that window (locations equal, tie-safe; metrics within the 1e-5 of the fp32 engines, because a
+ * batch may take another kernel form than a single epoch).  Argument checks as gacq_acquire_int8 and gacq_frontend_batch_dev, all
+ * made before anything is launched.  Asynchronous, so unlike gacq_acquire_int8 it cannot return GACQ_WARN_TIE_LIST_FULL: a caller
+ * that needs to know reads gacq_get_tie_stats()[2] after the call.  Memory: the library-owned buffer of front-end output, the
+ * front-end's intermediates and the search's two workspaces are each sized from the workspace limit on their own, so the call can
+ * hold up to four times that limit (less whenever the windows need less). */
+int gacq_scan_int8_dev(gacq_sig* sig, const void* d_iq_int8, long long nsamp_avail, const long long* starts, int nwin, size_t nsamp_in,
+                       double fs_in, double carrier_offset_hz, const double* taps, int ntaps, size_t nsamp_out, const int* items,
+                       int nitems, const double* dopplers, int nd, const double* item_bias_hz, int blocks, void* d_peaks);
+
 /* ---------------------------------------------------------------------------------------------
  * Time-domain long-code searches (SURVEY.md section 8f "next #3"): acquire-gps-l2cl.py:15-30,
  * acquire-glonass-l1-p.py / -l2-p.py:15-33.  For candidate k:
