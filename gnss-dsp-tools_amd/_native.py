@@ -203,6 +203,9 @@ SYMBOLS = {
     # synthetic recordings (simulate.py): the gacq_sim_sat array as a plain address
     "gacq_simulate_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_ulonglong,
                                          ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]),
+    # recording ingest (ingest.py): the gacq_ingest_fmt as a plain address
+    "gacq_ingest_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                                       ctypes.c_longlong, ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
     "gacq_stream_probe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, c_double_p]),
     "gacq_stream_create_cu_mask": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     "gacq_stream_destroy": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p]),

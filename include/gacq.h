@@ -592,6 +592,50 @@ typedef struct gacq_sim_sat {
 int gacq_simulate_dev(gacq_ctx* ctx, const gacq_sim_sat* sats, int K, double fs, double sigma, unsigned long long seed, long long j0,
                       long long n, int out_complex64, void* d_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Recording ingest (gacq_ingest.hip): packed, 8-bit, 16-bit and float32 recordings, I/Q or real IF, to the interleaved signed 8-bit
+ * I/Q (or complex64) that every other entry point takes.  Output sample m is an exact function of (format, gain, absolute sample
+ * index m) -- the same bytes however a caller cuts the recording into calls.
+ * Values.  A container turns the bytes at d_in into values v[0], v[1], ...:
+ *     GACQ_INGEST_S8 the int8; GACQ_INGEST_U8 byte - 128; GACQ_INGEST_S16 little-endian int16; GACQ_INGEST_F32 little-endian float32;
+ *     GACQ_INGEST_PACKED: bits = 1, 2 or 4 per code, 8 / bits codes per byte; code i of a byte is (byte >> (8 - bits (i + 1))) & (2^bits - 1)
+ *       with msb_first, (byte >> (bits i)) & (2^bits - 1) without; v = lut[code].
+ * I/Q (real = 0): sample j is u(j) = v[2j] + i v[2j + 1].
+ * Real IF (real != 0; S8, U8 and PACKED only, so |v| <= 128): x[n] = v[n], x[n] = 0 for n < 0; an fs/4 down-shift, a half-band low-pass
+ * and decimation by two, all in integers (Gaussian integers, int32 per component):
+ *     acc(m) = sum_{k = -21..21} g[k] x[2m - k] (-i)^(2m - k),        u(m) = acc(m) 2^-14,
+ *     g[-k] = g[k], g[0] = 16384, g[even k != 0] = 0, g[1, 3, .., 21] = 10382, -3333, 1852, -1175, 774, -506, 320, -188, 97, -40, 9:
+ *     rint(16384 h[k] / h[0]) of the 47-tap Hann-windowed sinc with its cutoff at fs/4 (gacq_firwin_hann(47, 0.5)); the taps sum to 32768.
+ *   |acc| <= 128 * 53736 < 2^23, so u(m) is exact in fp32.  The output rate is fs/2 and a signal at IF f appears at f - fs/4.
+ * conj != 0 negates the imaginary part of u (spectral inversion), in either mode.
+ * Output: complex64 float32(u) * float32(gain) per component -- one fp32 multiply, nothing fused (out_complex64 != 0, d_out 8-byte
+ * aligned) -- or interleaved int8 clip(rint(.), -127, 127) of exactly those values, ties to even, NaN to 0.
+ * d_in holds input samples in_first .. in_first + in_count - 1 (a complex sample in I/Q mode, a real one in real mode) and starts on a
+ * byte boundary: in_first times the bits per sample is a multiple of 8.  Output samples out_first .. out_first + n_out - 1 are written
+ * to d_out; I/Q output m needs input m, real output m needs inputs 2m - 21 .. 2m + 21 (those below 0 are zero).  An input that is
+ * needed and not present GACQ_ERR_SHORT_INPUT; an unknown container, bits outside {1, 2, 4}, real mode with S16 or F32, a gain that is
+ * not finite and positive (as a double and as a float), a negative index or count or one above 2^48, an in_first off a byte boundary,
+ * a misaligned complex64 d_out, a NULL pointer GACQ_ERR_BAD_ARG.  Everything is checked on the host before anything is launched.
+ * n_out = 0 does nothing.  One launch on the ctx stream, no staging, no state; asynchronous.
+ * ------------------------------------------------------------------------------------------- */
+#define GACQ_INGEST_S8 0
+#define GACQ_INGEST_U8 1
+#define GACQ_INGEST_S16 2
+#define GACQ_INGEST_F32 3
+#define GACQ_INGEST_PACKED 4
+typedef struct gacq_ingest_fmt {
+  int container;                   /* GACQ_INGEST_* */
+  int real;                        /* 0: I/Q pairs; otherwise real IF samples */
+  int bits;                        /* PACKED: bits per code, 1, 2 or 4 */
+  int msb_first;                   /* PACKED: the first code of a byte is in its top bits */
+  int conj;                        /* negate the imaginary part */
+  int pad[3];
+  int8_t lut[16];                  /* PACKED: value of each code */
+} gacq_ingest_fmt;
+
+int gacq_ingest_dev(gacq_ctx* ctx, const gacq_ingest_fmt* fmt, const void* d_in, long long in_first, long long in_count,
+                    long long out_first, long long n_out, double gain, int out_complex64, void* d_out);
+
 /* Per-stage GPU time from HIP events recorded on the launch stream (profiling aid for bench.py).
  * Stages: 0 mix/forward, 1 forward FFT (rocFFT), 2 conj-multiply, 3 inverse FFT (rocFFT),
  *         4 magnitude/peak reduce, 5 best-over-Doppler, 6 fused correlate kernel (LDS FFT). */
