@@ -115,6 +115,27 @@ __device__ __forceinline__ float wave_add_f32(float v) {
   const float c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 32)), d = __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 48));
   return (a + b) + (c + d);
 }
+// The same reductions with the four rows combined on DPP as well: row_bcast:15 adds lane 15 of rows 0 / 2 into every lane of rows
+// 1 / 3 (row_mask 0xa), row_bcast:31 adds lane 31 into rows 2 and 3 (row_mask 0xc), which leaves the wave's result in lane 63: one
+// v_readlane instead of four and no combine after it.  The sum is (r0 + r1) + (r2 + r3) like wave_add_f32's, so it is the same bits.
+#define GACQ_DPP_REDUCE_BCAST(OP)                                                                             \
+  asm volatile("s_nop 1\n\t" OP " %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"           \
+               "s_nop 1\n\t" OP " %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"           \
+               "s_nop 1\n\t" OP " %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"               \
+               "s_nop 1\n\t" OP " %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"                    \
+               "s_nop 1\n\t" OP " %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"                  \
+               "s_nop 1\n\t" OP " %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"                  \
+               "s_nop 1"                                                                                      \
+               : "+v"(x))
+__device__ __forceinline__ unsigned wave_max_u32_bcast(unsigned x) {
+  GACQ_DPP_REDUCE_BCAST("v_max_u32_dpp");
+  return __builtin_amdgcn_readlane(x, 63);
+}
+__device__ __forceinline__ float wave_add_f32_bcast(float v) {
+  unsigned x = __builtin_bit_cast(unsigned, v);
+  GACQ_DPP_REDUCE_BCAST("v_add_f32_dpp");
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(x, 63));
+}
 
 // 4-point DFT, forward W4 = -i (INV: +i).  ROTC: input c still needs its -/+i factor (folded into the adds).
 template <bool INV, bool ROTC> __device__ __forceinline__ void dft4(v2& a, v2& b, v2& c, v2& d) {
@@ -199,6 +220,113 @@ template <bool INV> __device__ __forceinline__ void dft16(v2 (&v)[16]) {
     v[13] = INV ? add_i(d0, t) : sub_i(d0, t);
     v[15] = INV ? sub_i(d0, t) : add_i(d0, t);
   }                                                                                           // -> X[k0+4k1] at v[4k0+k1]
+}
+
+// Planar forms of the last radix-4 layer of the inverse dft16: the same packed add / FMA on the same two operands, with
+// op_sel / neg bits that deliver the real parts of TWO outputs, then their imaginary parts, instead of (re, im) of one:
+//   pl_sum_re(s0, s1)  = (s0.re + s1.re, s0.re - s1.re) = (re a, re c)   of a = s0 + s1,   c = s0 - s1
+//   pl_sum_im(s0, s1)  = (s0.im + s1.im, s0.im - s1.im) = (im a, im c)
+//   pl_rot_re(d0, t)   = (d0.re - t.im, d0.re + t.im)   = (re b, re d)   of b = add_i(d0, t),  d = sub_i(d0, t)
+//   pl_rot_im(d0, t)   = (d0.im + t.re, d0.im - t.re)   = (im b, im d)
+// and with the real scale h = hh.lo = -hh.hi in an SGPR pair (row 2 of dft16):
+//   pl_fma_re(s0, s1, hh) = (s0.re + h s1.re, s0.re - h s1.re) = (re, re) of fma_lo(s0, s1, hh), fma_hi(s0, s1, hh)
+//   pl_fma_im(s0, s1, hh) = (s0.im + h s1.im, s0.im - h s1.im)
+//   pl_ih_re(d0, t, hh)   = (d0.re - h t.im, d0.re + h t.im)   = (re, re) of add_ih(d0, t, hh), sub_ih(d0, t, hh)
+//   pl_ih_im(d0, t, hh)   = (d0.im + h t.re, d0.im - h t.re)
+// Every half is one rounding of the expression the (re, im) form computes (a - b is a + (-b); -h is the stored hh.hi), so the
+// values are the same bits.
+__device__ __forceinline__ v2 pl_sum_re(v2 a, v2 b) {
+  v2 r;
+  asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ v2 pl_sum_im(v2 a, v2 b) {
+  v2 r;
+  asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ v2 pl_rot_re(v2 a, v2 b) {
+  v2 r;
+  asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[0,1] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ v2 pl_rot_im(v2 a, v2 b) {
+  v2 r;
+  asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ v2 pl_fma_re(v2 acc, v2 x, v2 hh) {
+  v2 r;
+  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(x), "s"(hh), "v"(acc));
+  return r;
+}
+__device__ __forceinline__ v2 pl_fma_im(v2 acc, v2 x, v2 hh) {
+  v2 r;
+  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,1] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(x), "s"(hh), "v"(acc));
+  return r;
+}
+__device__ __forceinline__ v2 pl_ih_re(v2 a, v2 b, v2 hh) {
+  v2 r;
+  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(b), "s"(hh), "v"(a));
+  return r;
+}
+__device__ __forceinline__ v2 pl_ih_im(v2 a, v2 b, v2 hh) {
+  v2 r;
+  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,1] op_sel_hi:[0,1,1]" : "=v"(r) : "v"(b), "s"(hh), "v"(a));
+  return r;
+}
+// |z|^2 of two values held planar: (re0, re1), (im0, im1) -> (re0^2 then fma(im0, im0, .), same for 1): norm2's two roundings
+__device__ __forceinline__ v2 norm2_planar(v2 re, v2 im) {
+  v2 t, r;
+  asm("v_pk_mul_f32 %0, %2, %2\n\t"
+      "v_pk_fma_f32 %1, %3, %3, %0"
+      : "=&v"(t), "=v"(r)
+      : "v"(re), "v"(im));
+  return r;
+}
+
+// Inverse dft16 whose last radix-4 layer leaves its outputs planar: pl[j] = (re X[j], re X[j + 8]), pl[8 + j] = (im X[j], im X[j + 8]),
+// j = 0..7, for the caller that only wants |X[k]|^2 (two per v_pk_mul_f32 + v_pk_fma_f32).  Everything up to that layer is
+// dft16<true>'s code; the layer's operand table, per row k0 (outputs X[k0 + 4 k1], k1 = 0..3 -> a, b, c, d):
+//   rows 0, 1, 3:  a, c = s0 +- s1            -> pl_sum_{re,im}(s0, s1) into pl[k0]         b, d = d0 +- i t         -> pl_rot_{re,im}(d0, t) into pl[k0 + 4]
+//   row 2:         a, c = s0 +- h s1 (FMA)    -> pl_fma_{re,im}(s0, s1, hh) into pl[2]      b, d = d0 +- i h t (FMA) -> pl_ih_{re,im}(d0, t, hh) into pl[6]
+// v is left holding the intermediate values.
+__device__ __forceinline__ void dft16_inv_planar(v2 (&v)[16], v2 (&pl)[16]) {
+  constexpr bool INV = true;
+#pragma unroll
+  for (int n0 = 0; n0 < 4; n0++) dft4<INV, false>(v[n0], v[n0 + 4], v[n0 + 8], v[n0 + 12]);
+  const v2 hh = {0.70710678118654752f, -0.70710678118654752f};
+  v[5] = cmul_k(v[5], w16<INV, 1>());   v[13] = cmul_k(v[13], w16<INV, 3>());
+  v[7] = cmul_k(v[7], w16<INV, 3>());   v[15] = cmul_k(v[15], w16<INV, 9>());
+  const v2 c1 = add_i(v[6], v[6]);
+  const v2 b2 = add_i(v[9], v[9]);
+  const v2 d2 = sub_i(v[11], v[11]);
+  const v2 c3 = sub_i(v[14], v[14]);
+  {  // row k0 = 0
+    const v2 s0 = v[0] + v[2], d0 = v[0] - v[2];
+    const v2 s1 = v[1] + v[3], t = v[1] - v[3];
+    pl[0] = pl_sum_re(s0, s1);  pl[8] = pl_sum_im(s0, s1);
+    pl[4] = pl_rot_re(d0, t);   pl[12] = pl_rot_im(d0, t);
+  }
+  {  // row k0 = 1
+    const v2 s0 = fma_lo(v[4], c1, hh), d0 = fma_hi(v[4], c1, hh);
+    const v2 s1 = v[5] + v[7], t = v[5] - v[7];
+    pl[1] = pl_sum_re(s0, s1);  pl[9] = pl_sum_im(s0, s1);
+    pl[5] = pl_rot_re(d0, t);   pl[13] = pl_rot_im(d0, t);
+  }
+  {  // row k0 = 2
+    const v2 s0 = add_i(v[8], v[10]);
+    const v2 d0 = sub_i(v[8], v[10]);
+    const v2 s1 = b2 - d2, t = b2 + d2;
+    pl[2] = pl_fma_re(s0, s1, hh);  pl[10] = pl_fma_im(s0, s1, hh);
+    pl[6] = pl_ih_re(d0, t, hh);    pl[14] = pl_ih_im(d0, t, hh);
+  }
+  {  // row k0 = 3
+    const v2 s0 = fma_hi(v[12], c3, hh), d0 = fma_lo(v[12], c3, hh);
+    const v2 s1 = v[13] + v[15], t = v[13] - v[15];
+    pl[3] = pl_sum_re(s0, s1);  pl[11] = pl_sum_im(s0, s1);
+    pl[7] = pl_rot_re(d0, t);   pl[15] = pl_rot_im(d0, t);
+  }
 }
 
 // cos/sin(2 pi m / P) for the odd primes used as outer radices

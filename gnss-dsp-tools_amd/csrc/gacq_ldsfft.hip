@@ -63,6 +63,8 @@ __device__ __forceinline__ void apply_table(v2 (&v)[kR], const v2 (&pw)[15]) {
 // conjugated for an inverse transform) instead of being rebuilt from wa / wb by 14 complex products per pass.
 // bit 2 = the pass-2 powers are read from an LDS table (tb2[16 (k - 1)], tb2 already offset by the lane's class t & 15).
 // bit 3 = rising wave priority through the row (F4K_PRIO above).
+// bit 4 = (inverse only) the last radix-4 layer leaves its outputs planar in *pl instead of in v (dft16_inv_planar, gacq_cplx.h):
+// pl[j] = (re X[t + 256 j], re X[t + 256 (j + 8)]), pl[8 + j] the imaginary parts.  Set by the fused kernel's item loop only.
 // Rising wave priority through the segments of a 4096-point row (PRE bit 3 of fft4096; the caller resets it to GACQ_F4K_P4 at the top
 // of its row loop): after the exchange-1 writes | after the exchange-2 writes | after the exchange-2 reads have been issued.  The four
 // waves of a SIMD belong to four independent workgroups; letting the one that is furthest into its row issue first keeps the workgroups
@@ -86,7 +88,8 @@ __device__ __forceinline__ void apply_table(v2 (&v)[kR], const v2 (&pw)[15]) {
 // the run-to-run noise, 0-2 %: not applied there.)
 template <bool INV, int PRE = 0>
 __device__ __forceinline__ void fft4096(v2 (&v)[kR], v2* lds, v2 wa, v2 wb, const v2 (*pa)[15] = nullptr, const v2 (*pb)[15] = nullptr,
-                                        int t = -1, const v2* tb2 = nullptr) {
+                                        int t = -1, const v2* tb2 = nullptr, v2 (*pl)[kR] = nullptr) {
+  static_assert(!(PRE & 16) || INV, "planar tail: inverse transform only");
   if (t < 0) t = threadIdx.x;                       // lane index within the 256-lane group that owns this transform
   if (INV && !(PRE & 1)) wa.y = -wa.y;
   if (INV && !(PRE & 2)) wb.y = -wb.y;
@@ -119,7 +122,8 @@ __device__ __forceinline__ void fft4096(v2 (&v)[kR], v2* lds, v2 wa, v2 wb, cons
     for (int j = 0; j < kR; j++) v[j] = LDS_LD(lds[t + kPitch * j]);
     F4K_PRIO((PRE & 8) ? GACQ_F4K_P3 : -1);
   }
-  dft16<INV>(v);
+  if (PRE & 16) dft16_inv_planar(v, *pl);
+  else dft16<INV>(v);
 }
 
 
@@ -871,6 +875,9 @@ __global__ __launch_bounds__(kBlock, MINW) void lds_correlate_kernel(const float
 #ifndef GACQ_F4K_RING
 #define GACQ_F4K_RING 32  // item loop of the fused kernel: rows between two combines of the per-wave partials (1 = after every row, A/B only)
 #endif
+#ifndef GACQ_F4K_EPILOGUE
+#define GACQ_F4K_EPILOGUE 1  // item loop of the fused kernel: planar last layer, packed squared magnitudes, all-DPP wave reductions (0 = the (re, im) epilogue, A/B only)
+#endif
 
 // ---- N = 4096, one block, one carrier: forward + correlate in ONE kernel ---------------------------------------------------
 // Workgroup = (epoch, Doppler bin, chunk of pch items).  Prologue: load the x window, table-NCO mix (fp64 index as in
@@ -974,23 +981,46 @@ __global__ __launch_bounds__(kBlock, MINW) void lds_fused4k_kernel(const float2*
     for (int jp = 0; jp < kR / 2; jp++) ld_pair(cres, lane_off, jp, v[2 * jp], v[2 * jp + 1]);
 #pragma unroll
     for (int jj = 0; jj < kR; jj++) v[jj] = cmul(v[jj], xr[jj]);
-    if (PREA) fft4096<true, GACQ_PRE4K>(v, lds, wa, wb, reinterpret_cast<const v2(*)[15]>(pwa), nullptr, -1, s_tw2 + (t & 15));
-    else fft4096<true>(v, lds, wa, wb);
     // lane t holds lags t + 256 k.  The 1/N of ifft is a power of two: applied once to the reduced values.
     float m[kR];
+#if GACQ_F4K_EPILOGUE
+    // Epilogue (GACQ_F4K_EPILOGUE): the transform's last layer delivers (re, re) / (im, im) pairs of lags k and k + 8, so that two
+    // squared magnitudes cost one v_pk_mul_f32 + one v_pk_fma_f32 (norm2's two roundings each) instead of two v_mul_f32 + two
+    // v_fmac_f32; m[k] is still lag t + 256 k (a renaming).  The sum over k stays the sequential chain, and the wave reductions
+    // combine the four rows on DPP too.  Every value is the same bits as with the (re, im) epilogue.  23 VALU instructions a row less
+    // (439 -> 416, SQ_INSTS_VALU agrees); headline step 1.012 x in the medians, every run above every run of the loop before it on two
+    // boxes (profiles/r15_fused4k_epilogue_ab.log).
+    v2 pl[kR];
+    if (PREA) fft4096<true, GACQ_PRE4K | 16>(v, lds, wa, wb, reinterpret_cast<const v2(*)[15]>(pwa), nullptr, -1, s_tw2 + (t & 15), &pl);
+    else fft4096<true, 16>(v, lds, wa, wb, nullptr, nullptr, -1, nullptr, &pl);
+#pragma unroll
+    for (int k = 0; k < kR / 2; k++) {
+      const v2 q = norm2_planar(pl[k], pl[k + kR / 2]);
+      m[k] = __builtin_amdgcn_sqrtf(q.x);                           // np.absolute(ifft(...)) * N
+      m[k + kR / 2] = __builtin_amdgcn_sqrtf(q.y);
+    }
+#else
+    if (PREA) fft4096<true, GACQ_PRE4K>(v, lds, wa, wb, reinterpret_cast<const v2(*)[15]>(pwa), nullptr, -1, s_tw2 + (t & 15));
+    else fft4096<true>(v, lds, wa, wb);
 #pragma unroll
     for (int k = 0; k < kR; k++) {
       const v2 r = v[rev16(k)];
       m[k] = __builtin_amdgcn_sqrtf(norm2(r));                      // np.absolute(ifft(...)) * N
     }
+#endif
     float sum_f = m[0];
 #pragma unroll
     for (int k = 1; k < kR; k++) sum_f += m[k];
     float wmaxf;
     unsigned widx;
+#if GACQ_F4K_EPILOGUE
+    wave_first_max<kR, wave_max_u32_bcast>(m, (unsigned)__builtin_amdgcn_readfirstlane(t & ~63), 1u, 256u, tie_scale, wmaxf, widx);
+    const float wsum = wave_add_f32_bcast(sum_f * inv_n);
+#else
     wave_first_max(m, (unsigned)__builtin_amdgcn_readfirstlane(t & ~63), 1u, 256u, tie_scale, wmaxf, widx);
-    const unsigned wmax = __builtin_bit_cast(unsigned, wmaxf * inv_n);
     const float wsum = wave_add_f32(sum_f * inv_n);
+#endif
+    const unsigned wmax = __builtin_bit_cast(unsigned, wmaxf * inv_n);
     const int slot = (p - p0) & (kRing - 1);
     if ((t & 63) == 0) { s_rpeak[slot][t >> 6] = __builtin_bit_cast(float, wmax); s_ridx[slot][t >> 6] = (int)widx; s_rsum[slot][t >> 6] = wsum; }
     lds_barrier();     // also orders this item's exchange-2 reads before the next item's exchange-1 writes

@@ -19,14 +19,15 @@ __device__ __forceinline__ v2 ld2(const float2* p) { return *reinterpret_cast<co
 // smallest k with a non-empty mask and its lowest lane are the smallest lag attaining the maximum (np.argmax returns the first
 // maximum, acquire-gps-l1.py:34).  24 VALU instructions instead of the 47 of a running (value, index) pair per lane; the
 // bookkeeping runs on the scalar unit.  Magnitudes are >= 0, so their bit patterns order like the values.
-template <int kR>
+// WMAX: the wave-wide maximum (wave_max_u32, or wave_max_u32_bcast where the kernel has been checked with it).
+template <int kR, unsigned (*WMAX)(unsigned) = wave_max_u32>
 __device__ __forceinline__ void wave_first_max(const float (&m)[kR], unsigned base, unsigned mult, unsigned kstride, float tie_scale,
                                                float& wmaxf, unsigned& widx) {
   float lmax = __builtin_fmaxf(__builtin_fmaxf(m[0], m[1]), m[2]);
 #pragma unroll
   for (int k = 3; k + 1 < kR; k += 2) lmax = __builtin_fmaxf(__builtin_fmaxf(lmax, m[k]), m[k + 1]);
   lmax = __builtin_fmaxf(lmax, m[kR - 1]);
-  wmaxf = __builtin_bit_cast(float, wave_max_u32(__builtin_bit_cast(unsigned, lmax)));
+  wmaxf = __builtin_bit_cast(float, WMAX(__builtin_bit_cast(unsigned, lmax)));
   // Tie-safe locations: the compare runs against thr = (1 - eps) * maximum instead of the maximum itself.  When exactly one entry
   // passes -- all but about one row in 10^4 -- it is the maximum and its mask is its location; the masks of all k are folded on the
   // scalar unit (seen: lanes with an entry, dup: lanes with two) to tell.  Otherwise the row is tagged ambiguous (kTieBit; the
