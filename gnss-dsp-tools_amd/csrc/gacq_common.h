@@ -210,7 +210,7 @@ enum class Form {
 };
 struct SearchPlan {
   Form form = Form::Rocfft;
-  // N = 16384, forms Lds / Fused16k: 32 = the radix-32 transform of gacq_lds16k.hip (default), 16 = the radix-16 one of gacq_ldsfft.hip
+  // N = 16384, forms Lds / Fused16k: 32 = the radix-32 transform of gacq_lds16k.hip (default), 16 = the radix-16 one of gacq_lds16k_r16.hip
   // (GACQ_OPT_LDS_VARIANT = 16: B1I 0-5 % slower, GLONASS within 2 % either way in the same process -- the in-run A/B of bench.py,
   // roofline.ab.n16384_transform); 0 otherwise
   int radix16k = 0;
@@ -224,24 +224,21 @@ int verify_search(gacq_sig* sig, const SearchPlan& plan, XSrc d_x, size_t nsamp,
 void stage_begin(gacq_ctx* ctx, int stage);
 void stage_end(gacq_ctx* ctx);
 
-// LDS-resident FFT engine (gacq_ldsfft.hip): supported lengths and the two launches.
+// LDS-resident FFT engine: the lengths it serves (4096 and 16384), and the launches of the N = 4096 kernels (gacq_ldsfft.hip).
 bool lds_supported(int N);
-int lds_code_spectra(gacq_ctx* ctx, const float2* replica_rows, float2* perm, int nprn, int N);      // code spectra in the LDS engines' layout: the replicas through their own forward transform
+int lds_code_spectra(gacq_ctx* ctx, const float2* replica_rows, float2* perm, int nprn);      // code spectra in the LDS engines' layout: the replicas through their own forward transform
 // X[row][k] = conj(FFT_N(x_window * nco))   rows = ((e*F + f)*D + d)*B + b
-int lds_forward(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, int n, int N, const double* d_freq,
+int lds_forward(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, int n, const double* d_freq,
                 int FD, int B, const float2* tab, float2* X);
 // rows[(e*P + p)*D + d] = reduce_k sum_b | IFFT_N(C_p * X[e,f(p),d,b]) | / N
-// N = 16384 with one carrier per item (F == P): forward + correlate in one kernel, no X buffer
-int lds_fused_search(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, int n, int N, const float2* spectra, const int* d_items,
-                     const int* d_fset, const double* d_freq, const float2* tab, int nitems, int D, int B, RowRec* rows, float tie_scale);
-// N = 4096, B == 1, one carrier: forward + correlate in one kernel, no X buffer
+// B == 1, one carrier: forward + correlate in one kernel, no X buffer
 int lds_fused4k_search(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, const float2* spectra, const int* d_items,
                        const double* d_freq, const float2* tab, int nitems, int D, RowRec* rows, float tie_scale);
 int lds_correlate(gacq_ctx* ctx, const float2* X, const float2* spectra, const int* d_items, const int* d_fset,
-                  int nepoch, int nitems, int F, int D, int B, int N, RowRec* rows, float tie_scale, float* q_out = nullptr);
+                  int nepoch, int nitems, int F, int D, int B, RowRec* rows, float tie_scale, float* q_out = nullptr);
 
-// N = 16384 as 32 x 32 x 16 in one 512-thread workgroup (gacq_lds16k.hip): the radix-32 counterparts of the lds_* entry points above,
-// which run the radix-16 form at that length
+// N = 16384 as 32 x 32 x 16 in one 512-thread workgroup (gacq_lds16k.hip): the radix-32 counterparts of the lds_* entry points above.
+// *_fused_search: one carrier per item (F == P), forward + correlate in one kernel, no X buffer
 int r32_code_spectra(gacq_ctx* ctx, const float2* replica_rows, float2* perm, int nprn);
 int r32_forward(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, int n, const double* d_freq, int FD, int B, const float2* tab,
                 float2* X);
@@ -250,10 +247,19 @@ int r32_fused_search(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, i
 int r32_correlate(gacq_ctx* ctx, const float2* X, const float2* spectra, const int* d_items, const int* d_fset, int nepoch, int nitems,
                   int F, int D, int B, RowRec* rows, float tie_scale, float* q_out);
 int r32_debug_nco(gacq_ctx* ctx, int n, const double* d_freq, bool fused, int* d_idx);
+// ... and as 16 x 16 x 16 x 4 in one 1024-thread workgroup (gacq_lds16k_r16.hip, GACQ_OPT_LDS_VARIANT = 16): the radix-16 ones
+int r16_code_spectra(gacq_ctx* ctx, const float2* replica_rows, float2* perm, int nprn);
+int r16_forward(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, int n, const double* d_freq, int FD, int B, const float2* tab,
+                float2* X);
+int r16_fused_search(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch, int n, const float2* spectra, const int* d_items,
+                     const int* d_fset, const double* d_freq, const float2* tab, int nitems, int D, int B, RowRec* rows, float tie_scale);
+int r16_correlate(gacq_ctx* ctx, const float2* X, const float2* spectra, const int* d_items, const int* d_fset, int nepoch, int nitems,
+                  int F, int D, int B, RowRec* rows, float tie_scale, float* q_out);
+int r16_debug_nco(gacq_ctx* ctx, int n, const double* d_freq, bool fused, int* d_idx);
 
-// test hook (gacq_debug_nco_indices): the forward kernel's own NCO index expression for one row, d_idx[N]; fused: the
+// test hook (gacq_debug_nco_indices): the forward kernel's own NCO index expression for one row, d_idx[N]; fused (r32 / r16): the
 // one-kernel N = 16384 search
-int lds_debug_nco(gacq_ctx* ctx, int N, int n, const double* d_freq, bool fused, int* d_idx);
+int lds_debug_nco(gacq_ctx* ctx, int n, const double* d_freq, int* d_idx);
 int split_debug_nco(gacq_ctx* ctx, int N, int n, const double* d_freq, int* d_idx);
 
 // front-end carrier wipe-off alone (gacq_frontend.hip): int8 I/Q on the device -> complex64, fixed-point table NCO

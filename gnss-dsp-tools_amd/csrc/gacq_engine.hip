@@ -727,7 +727,7 @@ static int build_signal(gacq_ctx* ctx, const gacq_sigdesc* desc, const std::vect
     });
   if (rc == GACQ_OK && lds_supported(N))      // N = 16384: the default radix-32 form's order
     rc = ensure_spectra(s, &s->spectra_lds, false, [](gacq_sig* s, float2* rows, float2* c) {
-      return s->N == 16384 ? r32_code_spectra(s->ctx, rows, c, s->nprn) : lds_code_spectra(s->ctx, rows, c, s->nprn, s->N);
+      return s->N == 16384 ? r32_code_spectra(s->ctx, rows, c, s->nprn) : lds_code_spectra(s->ctx, rows, c, s->nprn);
     });
   if (rc == GACQ_OK && !R && !lds_supported(N)) rc = natural_spectra(s);      // lengths only the rocFFT pipeline serves
   if (rc != GACQ_OK) { gacq_signal_destroy(s); return rc; }
@@ -882,7 +882,7 @@ int code_spectra(gacq_sig* s, const SearchPlan& plan, const float2** out) {
     case Form::Fused4k: case Form::Fused16k: case Form::Lds:
       if (plan.radix16k == 16)
         rc = ensure_spectra(s, &s->spectra_lds16, false, [](gacq_sig* s, float2* rows, float2* c) {
-          return lds_code_spectra(s->ctx, rows, c, s->nprn, s->N);
+          return r16_code_spectra(s->ctx, rows, c, s->nprn);
         });
       *out = plan.radix16k == 16 ? s->spectra_lds16 : s->spectra_lds;
       break;
@@ -1000,7 +1000,7 @@ int launch_search(gacq_sig* sig, XSrc xs, const float2* d_x, size_t nsamp, int n
 
   const int R = split_radix(N);
   const int chunksN = (N + kBlock * 8 - 1) / (kBlock * 8);
-  const bool r32 = plan.radix16k == 32;
+  const int radix = plan.radix16k;      // 32 / 16 at N = 16384, 0 (the lds_* kernels) at N = 4096
   const int* d_items = (const int*)ctx->items.p;
   const int* d_fset = (const int*)ctx->fset.p;
   const double* d_freq = (const double*)ctx->freq.p;
@@ -1014,18 +1014,21 @@ int launch_search(gacq_sig* sig, XSrc xs, const float2* d_x, size_t nsamp, int n
     switch (plan.form) {
       case Form::Fused16k:
         rc = timed(ctx, 6, [&] {
-          return r32 ? r32_fused_search(ctx, xe, nsamp, ne, n, C, d_items, d_fset, d_freq, tab, P, D, B, rows, tscale)
-                     : lds_fused_search(ctx, xe, nsamp, ne, n, N, C, d_items, d_fset, d_freq, tab, P, D, B, rows, tscale);
+          return radix == 32 ? r32_fused_search(ctx, xe, nsamp, ne, n, C, d_items, d_fset, d_freq, tab, P, D, B, rows, tscale)
+                             : r16_fused_search(ctx, xe, nsamp, ne, n, C, d_items, d_fset, d_freq, tab, P, D, B, rows, tscale);
         });
         break;
       case Form::Fused4k: rc = timed(ctx, 6, [&] { return lds_fused4k_search(ctx, xe, nsamp, ne, C, d_items, d_freq, tab, P, D, rows, tscale); }); break;
       case Form::Lds:
         rc = timed(ctx, 0, [&] {
-          return r32 ? r32_forward(ctx, xe, nsamp, ne, n, d_freq, F * D, B, tab, X) : lds_forward(ctx, xe, nsamp, ne, n, N, d_freq, F * D, B, tab, X);
+          return radix == 32 ? r32_forward(ctx, xe, nsamp, ne, n, d_freq, F * D, B, tab, X)
+               : radix == 16 ? r16_forward(ctx, xe, nsamp, ne, n, d_freq, F * D, B, tab, X)
+                             : lds_forward(ctx, xe, nsamp, ne, n, d_freq, F * D, B, tab, X);
         });
         if (rc == GACQ_OK) rc = timed(ctx, 6, [&] {
-          return r32 ? r32_correlate(ctx, X, C, d_items, d_fset, ne, P, F, D, B, rows, tscale, d_qrow)
-                     : lds_correlate(ctx, X, C, d_items, d_fset, ne, P, F, D, B, N, rows, tscale, d_qrow);
+          return radix == 32 ? r32_correlate(ctx, X, C, d_items, d_fset, ne, P, F, D, B, rows, tscale, d_qrow)
+               : radix == 16 ? r16_correlate(ctx, X, C, d_items, d_fset, ne, P, F, D, B, rows, tscale, d_qrow)
+                             : lds_correlate(ctx, X, C, d_items, d_fset, ne, P, F, D, B, rows, tscale, d_qrow);
         });
         break;
       case Form::Pfa: rc = timed(ctx, 0, [&] { return pfa_forward(ctx, xe, nsamp, rows_x, n, N, d_freq, F * D, B, tab, X, true); }); break;
@@ -1540,8 +1543,11 @@ int gacq_debug_nco_indices(gacq_sig* sig, int kernel, double doppler, double bia
       break;
     }
     case 2: case 4:      // N = 16384: the form of the transform a search would run (plan_search)
-      rc = (N == 16384 && lds16k_radix(ctx) == 32) ? r32_debug_nco(ctx, n, (const double*)ctx->freq.p, kernel == 4, d_idx)
-                                                   : lds_debug_nco(ctx, N, n, (const double*)ctx->freq.p, kernel == 4, d_idx);
+      if (!lds_supported(N) || (kernel == 4 && N != 16384))
+        rc = set_error(ctx, GACQ_ERR_UNSUPPORTED, "NCO index dump: no %sLDS forward kernel for N=%d", kernel == 4 ? "fused " : "", N);
+      else if (N != 16384) rc = lds_debug_nco(ctx, n, (const double*)ctx->freq.p, d_idx);
+      else if (lds16k_radix(ctx) == 32) rc = r32_debug_nco(ctx, n, (const double*)ctx->freq.p, kernel == 4, d_idx);
+      else rc = r16_debug_nco(ctx, n, (const double*)ctx->freq.p, kernel == 4, d_idx);
       break;
     case 3: rc = split_debug_nco(ctx, N, n, (const double*)ctx->freq.p, d_idx); break;
     case 5: rc = pfa_debug_nco(ctx, N, n, (const double*)ctx->freq.p, d_idx); break;

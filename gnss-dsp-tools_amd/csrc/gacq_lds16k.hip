@@ -14,7 +14,7 @@
 //   N y[t + 512 j] in register j of thread t.  Spectra (X, C_p) live in memory in the order the forward transform produces them
 //   ("physical lane-pair layout": element (t', r) at (r >> 1) * 1024 + 2 t' + (r & 1)): 16-byte accesses, 1 KiB per wave and
 //   instruction, no reordering pass anywhere.
-// Why this shape, and what it measured (round 6, profiles/r06_16k_radix32_experiments.log): the radix-16 form (gacq_ldsfft.hip: 1024
+// Why this shape, and what it measured (round 6, profiles/r06_16k_radix32_experiments.log): the radix-16 form (gacq_lds16k_r16.hip: 1024
 // threads x 16 points, 16 x 16 x 16 x 4, three exchanges) fills 16 waves x 128 registers with the code spectrum (32), the row (32) and
 // the accumulators (16), so its three sets of inter-pass twiddle powers are REBUILT per row (42 of a row's 237 complex products) and
 // every cheaper source (LDS or memory tables) cost more than it saved.  Eight waves x 256 registers hold the same row state

@@ -1,5 +1,6 @@
 // Helpers shared by the LDS-resident transform kernels (gacq_ldsfft.hip: N = 4096 and the inner rows of the split engines;
-// gacq_lds16k.hip: N = 16384): wave-level first maximum, one-instruction LDS accesses, the vmcnt-preserving barrier.
+// gacq_lds16k.hip, gacq_lds16k_r16.hip: N = 16384): wave-level first maximum, the radix-16 twiddle powers, one-instruction LDS accesses,
+// the vmcnt-preserving barrier.
 #pragma once
 #include "gacq_common.h"
 #include "gacq_cplx.h"
@@ -55,6 +56,22 @@ __device__ __forceinline__ void wave_first_max(const float (&m)[kR], unsigned ba
     }
     widx |= (unsigned)kTieBit;
   }
+}
+
+constexpr int kR = 16;                 // points per lane of the radix-16 kernels (gacq_ldsfft.hip, gacq_lds16k_r16.hip)
+
+// v[rev16(k)] *= w^k for k = 1..15, powers built with multiplication depth <= 4 from the table value.
+__device__ __forceinline__ void apply_powers(v2 (&v)[kR], v2 w1) {
+  const v2 w2 = cmul(w1, w1), w3 = cmul(w2, w1), w4 = cmul(w2, w2);
+  v[rev16(1)] = cmul(v[rev16(1)], w1);    v[rev16(2)] = cmul(v[rev16(2)], w2);    v[rev16(3)] = cmul(v[rev16(3)], w3);
+  const v2 w5 = cmul(w4, w1), w6 = cmul(w3, w3), w7 = cmul(w4, w3), w8 = cmul(w4, w4);
+  v[rev16(4)] = cmul(v[rev16(4)], w4);    v[rev16(5)] = cmul(v[rev16(5)], w5);    v[rev16(6)] = cmul(v[rev16(6)], w6);
+  v[rev16(7)] = cmul(v[rev16(7)], w7);
+  const v2 w9 = cmul(w8, w1), w10 = cmul(w5, w5), w11 = cmul(w8, w3), w12 = cmul(w6, w6);
+  v[rev16(8)] = cmul(v[rev16(8)], w8);    v[rev16(9)] = cmul(v[rev16(9)], w9);    v[rev16(10)] = cmul(v[rev16(10)], w10);
+  v[rev16(11)] = cmul(v[rev16(11)], w11); v[rev16(12)] = cmul(v[rev16(12)], w12);
+  const v2 w13 = cmul(w8, w5), w14 = cmul(w7, w7), w15 = cmul(w8, w7);
+  v[rev16(13)] = cmul(v[rev16(13)], w13); v[rev16(14)] = cmul(v[rev16(14)], w14); v[rev16(15)] = cmul(v[rev16(15)], w15);
 }
 
 // LDS accesses of the exchanges, one per instruction (GACQ_UNPAIR, gacq_cplx.h): LDS_LD for every read; LDS_ST1 for the writes of the

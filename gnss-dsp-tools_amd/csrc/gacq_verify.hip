@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kBlock, 2) void fused4k_c128_kernel(XSrc x, size_t 
   const double2 wa2 = tw[t], wb2 = tw[16 * (t & 15)];
   const cd wa = {wa2.x, wa2.y}, wb = {wb2.x, wb2.y};
   // pass-2 twiddle powers of the inverse transform, conj(W_256^c)^k for the 16 lane classes c = t & 15: built once per workgroup,
-  // read back from a 3.8 KB LDS table in the item loop (the trick of lds_fused4k_kernel<.., PREA>)
+  // read back from a 3.8 KB LDS table in the item loop (the trick of lds_fused4k_kernel)
   __shared__ cd s_tw2[15 * 16];
   if (t < 16) {
     cd pw[15];

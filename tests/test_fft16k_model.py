@@ -1,5 +1,5 @@
 """Host-side check of the N = 16384 engine's index algebra (CPU, no GPU): tools/model_fft16k.py replays the data movement of
-fft16k_fwd / ifft16k_* of gacq_ldsfft.hip -- every register/lane/LDS address of the three passes, the two wave-private transposes and
+fft16k_fwd / ifft16k_* of gacq_lds16k_r16.hip -- every register/lane/LDS address of the three passes, the two wave-private transposes and
 the cross-wave exchange -- in numpy.  The forward model must equal numpy.fft in the digit-permuted order the kernels store spectra in,
 the inverse model must undo it, and no LDS access may put two lanes of a 16-lane store group / 32-lane load group on one bank slot."""
 import importlib.util

@@ -155,9 +155,9 @@ def _kernel_resources(tmp_path, fragment):
 
 
 def test_fused_4096_kernel_resources_keep_four_workgroups_per_cu(tmp_path):
-    """lds_fused4k_kernel<4, true> runs four workgroups per CU, one wave of each per SIMD: at most 128 VGPRs, no accumulator
+    """lds_fused4k_kernel runs four workgroups per CU, one wave of each per SIMD: at most 128 VGPRs, no accumulator
     registers, no scratch, and four workgroups' LDS (transform buffer + pass-2 twiddle table + record ring) within the CU's 160 KiB."""
-    m = _kernel_resources(tmp_path, "lds_fused4k_kernelILi4ELb1E")
+    m = _kernel_resources(tmp_path, "lds_fused4k_kernelE")
     assert m["vgpr_count"] <= 128, m
     assert m["agpr_count"] == 0, m
     assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, m

@@ -1,4 +1,4 @@
-"""numpy model of the N = 16384 transforms of gacq_ldsfft.hip (forward DIF, inverse DIT, 16 wave-private 1024-point transforms + one
+"""numpy model of the N = 16384 transforms of gacq_lds16k_r16.hip (forward DIF, inverse DIT, 16 wave-private 1024-point transforms + one
 cross-wave radix-16 pass): checks the index algebra end to end against numpy.fft and every LDS access pattern for bank conflicts
 (ds_write_b64: 16-lane groups, 8-byte slot mod 16; ds_read_b64: 32-lane groups, slot mod 32).  Run: python tools/model_fft16k.py"""
 # numpy model of the wave-private 16384-point transforms (forward DIF, inverse DIT): checks the index algebra and LDS bank conflicts

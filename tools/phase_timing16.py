@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where the waves of the N = 16384 correlate kernel spend their cycles (diagnostic): needs a variant built with -DGACQ_PHASE_TIMING16,
    tools/build_variant.sh timing16 -DGACQ_PHASE_TIMING16 gacq_lds16k.hip ; python tools/variant.py timing16 tools/phase_timing16.py
-(radix-32 form; the radix-16 form: build gacq_ldsfft.hip with the flag instead and pass lds_variant=16)
+(radix-32 form; the radix-16 form: build gacq_lds16k_r16.hip with the flag instead and pass lds_variant=16)
 Prints shader-clock cycles per row, wave and phase (lane 0 of every wave, summed over all workgroups)."""
 import ctypes
 import os
