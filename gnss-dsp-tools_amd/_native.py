@@ -206,6 +206,14 @@ SYMBOLS = {
     # recording ingest (ingest.py): the gacq_ingest_fmt as a plain address
     "gacq_ingest_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                        ctypes.c_longlong, ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
+    # navigation data (navdata.py): host arrays and the gacq_vit_job array as plain addresses
+    "gacq_navsym_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gacq_navsym": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gacq_viterbi_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong]),
+    "gacq_viterbi_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                        ctypes.c_longlong, ctypes.c_void_p]),
     "gacq_stream_probe": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, c_double_p]),
     "gacq_stream_create_cu_mask": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
     "gacq_stream_destroy": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p]),

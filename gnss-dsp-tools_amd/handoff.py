@@ -1,7 +1,7 @@
 """Acquire-to-track hand-off: from a recording to running tracking channels, with no number typed by hand.
 
     python -m gnss_dsp_tools_amd.handoff <signal> [--prn|--channel LIST] [--doppler-search MIN,MAX,INCR] [--time MS]
-           [--min-metric X] [--min-ratio R] [--blocks M] [--loop-dwells A,B] [--out-dir DIR] FILE FS COFFSET
+           [--min-metric X] [--min-ratio R] [--blocks M] [--loop-dwells A,B] [--out-dir DIR] [--nav] FILE FS COFFSET
 
 runs the acquisition of ``python -m gnss_dsp_tools_amd.cli <signal>`` (same options, same output lines), refines every kept result on the
 raw recording (refine.py), prints one line per handed-off channel
@@ -10,7 +10,9 @@ raw recording (refine.py), prints one line per handed-off channel
 
 whose first fields are the arguments one would give ``python -m gnss_dsp_tools_amd.track``, and, with --out-dir, tracks all channels
 in one batched TrackLoop run and writes track-<tracker>-<item>.txt per channel: the lines that track command prints for exactly the
-values on the handoff line (the channels are built from the printed, rounded values).
+values on the handoff line (the channels are built from the printed, rounded values).  With --nav the channels are tracked as well
+and, for the trackers of navdata.FORMATS, the navigation frames of what was tracked are printed after the handoff lines, one
+``nav ...`` line per frame (navdata.py); without it the output is what it was before the option existed.
 
 Signals without a template tracker are refused: beidou-b2bi/-b2bq belong to chiptrack, and the long-code trackers (gps-l2cl,
 glonass-l1-p, glonass-l2-p) need a prior from another signal."""
@@ -21,7 +23,7 @@ import sys
 import numpy as np
 
 from . import _native as nat
-from . import acquire, chiptrack, codes, longtrack, refine as _refine, signals, trackloop
+from . import acquire, chiptrack, codes, longtrack, navdata, refine as _refine, signals, trackloop
 
 _RENAMED = {"xona-x1": "xona-x1p"}
 
@@ -131,6 +133,7 @@ def build_parser(sig):
     ap.add_argument("--blocks", type=int, default=16, help="1 ms blocks of the fine search (default %(default)s)")
     ap.add_argument("--loop-dwells", default="500,500", help="wide FLL, then narrow FLL, in milliseconds (default %(default)s)")
     ap.add_argument("--out-dir", default=None, help="track every handed-off channel and write track-<tracker>-<item>.txt there")
+    ap.add_argument("--nav", action="store_true", help="track every handed-off channel and print its navigation frames (trackers of navdata.FORMATS)")
     ap.add_argument("input_filename")
     ap.add_argument("sample_rate", type=float)
     ap.add_argument("carrier_offset", type=float)
@@ -165,12 +168,21 @@ def run(name, argv, out=sys.stdout):
             lines += [format_line(tracker, it, r) for it, r in refined]
             for line in lines:
                 print(line, file=out)
-            if a.out_dir is not None and loop is not None:
-                os.makedirs(a.out_dir, exist_ok=True)
-                for (it, _), recs in zip(refined, loop.run([x_dev] * loop.K)):
-                    with open(os.path.join(a.out_dir, "track-%s-%d.txt" % (tracker, it)), "w") as f:
-                        for line in trackloop.format_lines(tracker, recs):
-                            f.write(line + "\n")
+            nav = a.nav and tracker in navdata.FORMATS
+            if (a.out_dir is not None or nav) and loop is not None:
+                tracked = loop.run([x_dev] * loop.K)
+                if a.out_dir is not None:
+                    os.makedirs(a.out_dir, exist_ok=True)
+                    for (it, _), recs in zip(refined, tracked):
+                        with open(os.path.join(a.out_dir, "track-%s-%d.txt" % (tracker, it)), "w") as f:
+                            for line in trackloop.format_lines(tracker, recs):
+                                f.write(line + "\n")
+                if nav:
+                    frames = navdata.decode_many([(recs, tracker, it) for (it, _), recs in zip(refined, tracked)], engine=eng)
+                    more = [navdata.format_frame(tracker, it, fr) for (it, _), frs in zip(refined, frames) for fr in frs]
+                    for line in more:
+                        print(line, file=out)
+                    lines += more
         finally:
             if loop is not None:
                 loop.close()

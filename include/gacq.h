@@ -636,6 +636,64 @@ typedef struct gacq_ingest_fmt {
 int gacq_ingest_dev(gacq_ctx* ctx, const gacq_ingest_fmt* fmt, const void* d_in, long long in_first, long long in_count,
                     long long out_first, long long n_out, double gain, int out_complex64, void* d_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Navigation data from tracked prompts (gacq_navbits.hip; the framing is host code, gnss_dsp_tools_amd/navdata.py).
+ *
+ * gacq_navsym: symbol forming and bit synchronisation of K channels, one workgroup per channel.  Everything is host memory: the call
+ * uploads, launches one kernel, downloads and returns when the results are there.
+ *   prompts: the channels' prompt real parts one after the other, n[k] doubles of channel k (one per 1 ms record);
+ *   R[k] in 1..GACQ_NAV_MAX_R records per symbol; overlay[k * GACQ_NAV_MAX_R + r], r < R[k], the +-1 overlay over the records of a symbol;
+ *   align: NULL, or per channel -1 (search) or the alignment 0..R-1 to use.
+ * For alignment a in 0..R-1 and symbol m, all m with a + (m + 1) R <= n:
+ *     S[a][m] = sum_{r = 0..R-1} o[r] p[a + m R + r]      in fp64, r ascending, no fused multiply-add.
+ * A non-finite S is an erasure: it is left out of every maximum and sum below and quantises to 0.
+ *     e = the binary exponent (frexp) of the largest finite |S[a][m]| of the channel over all a and m (0 when that is 0);
+ *     t[a][m] = llrint(ldexp(|S[a][m]|, 40 - e));     E[a] = sum_m t[a][m] in int64 (wrapping; it cannot wrap for n <= 2^23);
+ *     a* = the a with the largest E[a], ties to the lowest a, or the caller's;     M = the number of non-erased symbols of a*;
+ *     A = ldexp(double(E[a*]) / double(M), e - 40), 0 when M = 0;
+ *     q[m] = clamp(rint((S[a*][m] * 48) / A), -127, 127) as int8, 0 when A = 0.  Positive q means bit 0.
+ * Results: align_out[k] = a*; E_out[k * GACQ_NAV_MAX_R + a] (0 for a >= R); A_out[k]; nq_out[k] = (n - a*) div R soft symbols of channel
+ * k in q_out from offset sum_{i < k} (n[i] div R[i]) (the room of alignment 0).
+ * Checked on the host before anything is allocated or launched (gacq_navsym_check makes the same checks and needs no device): K < 1, R
+ * outside 1..20, an overlay value other than +-1, align outside -1..R-1, a NULL pointer, n above 2^24 GACQ_ERR_BAD_ARG; n < 2 R - 1 (an
+ * alignment without a symbol) GACQ_ERR_SHORT_INPUT.
+ *
+ * gacq_viterbi_dev: J decodes of the K = 7, rate 1/2 convolutional code, one wave per job, state s in lane s.
+ *   Encoder: r[0] the current input bit, r[k] the input k steps before; G1 = 171 (octal) taps r0 r1 r2 r3 r6, G2 = 133 taps r0 r2 r3 r5 r6;
+ *   the output order is G1, G2; g2_inverted complements the G2 output.
+ *   Trellis: state = the last six inputs, newest in bit 5; input b takes p to ns = (p >> 1) | (b << 5), with r[i] = bit (6 - i) of p;
+ *   the predecessors of ns are p0 = (2 ns) & 63 and p1 = p0 | 1.
+ *   Metric: coded bit c expects the symbol 1 - 2c; branch metric exp0 q0 + exp1 q1 (int32); path metric max(pm[p0] + bm0, pm[p1] + bm1), a
+ *   tie takes p0; no renormalisation (at most 2^20 steps of at most 254 each).  start_state -1: every state starts at 0; otherwise
+ *   the other states start at -2^28.  end_state -1: the state with the best metric, ties to the lowest state.
+ *   coded[i], i < 2 steps: d_sym[sym_base + i], or with rows > 0 d_sym[sym_base + (i mod rows) cols + i div rows] (rows cols = 2 steps:
+ *   the de-interleaver of a block interleaver that is filled column-wise and read row-wise).
+ *   Written: d_bits[bit_base + k] = decoded bit first_bit + k, k < nbits (uint8 0 / 1), and d_metric[job] = the metric of the end state.
+ * d_sym (int8 [nsym]), d_bits (uint8 [nbits]) and d_metric (int32 [J]) are device memory, jobs is host memory.  One launch on the ctx
+ * stream; the call returns after it has finished.  Checked before anything is allocated or launched (gacq_viterbi_check: the same, no
+ * device): J < 1, steps outside 1..2^20, a gather that does not hold exactly the job's symbols, a state outside -1..63, a bit range
+ * outside the job's steps or the output, a NULL pointer GACQ_ERR_BAD_ARG; symbols outside d_sym GACQ_ERR_SHORT_INPUT.
+ * ------------------------------------------------------------------------------------------- */
+#define GACQ_NAV_MAX_R 20
+typedef struct gacq_vit_job {
+  long long sym_base;              /* offset of coded symbol 0 in d_sym */
+  long long bit_base;              /* offset in d_bits of the first bit written */
+  int steps;                       /* trellis steps, 1..2^20; two symbols each */
+  int rows, cols;                  /* gather; rows = 0: none */
+  int start_state;                 /* 0..63, or -1: every state starts at 0 */
+  int end_state;                   /* 0..63, or -1: the best metric */
+  int first_bit, nbits;            /* decoded bits first_bit .. first_bit + nbits - 1 are written */
+  int g2_inverted;
+} gacq_vit_job;
+
+int gacq_navsym_check(const double* prompts, const int* n, const int* R, const int8_t* overlay, const int* align, int K, const int* align_out,
+                      const long long* E_out, const double* A_out, const int8_t* q_out, const int* nq_out);
+int gacq_navsym(gacq_ctx* ctx, const double* prompts, const int* n, const int* R, const int8_t* overlay, const int* align, int K,
+                int* align_out, long long* E_out, double* A_out, int8_t* q_out, int* nq_out);
+int gacq_viterbi_check(const gacq_vit_job* jobs, int J, long long nsym, long long nbits);
+int gacq_viterbi_dev(gacq_ctx* ctx, const void* d_sym, long long nsym, const gacq_vit_job* jobs, int J, void* d_bits, long long nbits,
+                     void* d_metric);
+
 /* Per-stage GPU time from HIP events recorded on the launch stream (profiling aid for bench.py).
  * Stages: 0 mix/forward, 1 forward FFT (rocFFT), 2 conj-multiply, 3 inverse FFT (rocFFT),
  *         4 magnitude/peak reduce, 5 best-over-Doppler, 6 fused correlate kernel (LDS FFT). */
