@@ -206,6 +206,13 @@ SYMBOLS = {
     # recording ingest (ingest.py): the gacq_ingest_fmt as a plain address
     "gacq_ingest_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                        ctypes.c_longlong, ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
+    # interference mitigation (mitigate.py): the gacq_mitigate_cfg as a plain address
+    "gacq_mitigate_tile": (ctypes.c_int, [ctypes.c_int]),
+    "gacq_mitigate_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                                           ctypes.c_longlong, ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
+    "gacq_mitigate_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong,
+                                         ctypes.c_longlong, ctypes.c_longlong, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p]),
     # navigation data (navdata.py): host arrays and the gacq_vit_job array as plain addresses
     "gacq_navsym_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

@@ -637,6 +637,53 @@ int gacq_ingest_dev(gacq_ctx* ctx, const gacq_ingest_fmt* fmt, const void* d_in,
                     long long out_first, long long n_out, double gain, int out_complex64, void* d_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Interference mitigation (gacq_mitigate.hip): a pulse blanker and a spectral excision filter on the canonical recording, interleaved
+ * int8 I/Q (in_complex64 = 0) or complex64 in, int8 I/Q or complex64 out.  Every decision is a function of the absolute sample index, so
+ * the output does not depend on how the recording is cut into calls.  Input x(j), j >= 0; x(j) = 0 for j < 0.
+ * 1. Sanitise.  A sample with a non-finite component (complex64 input only) is replaced by 0 and counted as blanked, also with
+ *    blanking off; it is no hit below.
+ * 2. Blanking (blank_thr > 0).  p(j) = re^2 + im^2: int32 for int8 input; fp32 re*re + im*im, nothing fused, for complex64.
+ *    hit(j) = p(j) > blank_thr^2, the square formed once on the host in the arithmetic of the comparison: floor(blank_thr^2) of the
+ *    double for int8 input, float(blank_thr) * float(blank_thr) in fp32 for complex64.
+ *    z(j) = 0 when hit(j + d) holds for some |d| <= hold (0..64), else x(j).  Without blanking z = the sanitised x.
+ * 3. Excision (nfft != 0).  N = nfft a power of two in 64..4096, H = N / 2, w[n] = sin(pi (n + 0.5) / N) (w[n]^2 + w[n + H]^2 = 1).
+ *    Frame f >= 0 covers inputs (f - 1) H .. (f + 1) H - 1:  X_f = FFT_N(w z),  P_f[k] = |X_f[k]|^2,  med_f = the (N/2)-th smallest of
+ *    the N values P_f[k] (1-based: the lower median).  Bin k is hit when P_f[k] > ratio med_f (strict: an all-zero frame excises
+ *    nothing); every hit bin and its `guard` (0..8) neighbours on either side, circular in k, are set to 0.  y_f = w IFFT_N(X_f).
+ *    Output sample j of block q = j div H is y_q[j - (q - 1) H] + y_{q+1}[j - q H].  Without excision y = z.
+ * 4. Output, as in ingest: complex64 float32(y) * float32(gain) per component, one multiply, nothing fused; or int8
+ *    clip(rint(.), -127, 127) of exactly that value, ties to even, NaN to 0.
+ * 5. Statistics.  d_stats (NULL, or three uint64 that the caller zeroed; added to with integer atomics): [0] blanked = the samples j of
+ *    the output range whose z(j) was forced to 0 (sanitised or under a hit's hold); [1] frames = the frames f with
+ *    out_first <= f H < out_first + n_out (the frames the call owns); [2] bins = the zeroed bins over the owned frames.  d_frame_bins
+ *    (NULL, or one uint32 per owned frame, in frame order) receives each owned frame's zeroed-bin count.  The totals of any partition
+ *    of the outputs into calls sum to those of one call.
+ * d_in holds input samples in_first .. in_first + in_count - 1.  With excision, output block q needs inputs (q - 1) H - hold ..
+ * (q + 2) H - 1 + hold; without, output j needs j - hold .. j + hold; inputs below 0 are zero.  A needed input that is not present
+ * GACQ_ERR_SHORT_INPUT: a recording ends at the last output whose support is present.  Both stages off, nfft not a power of two in
+ * 64..4096, a ratio that is not finite or <= 1, blank_thr negative or not finite, hold outside 0..64, guard outside 0..8, a gain that is
+ * not finite and positive (as a double and as a float), an index or count below 0 or above 2^48, a complex64 buffer off 8 bytes, a NULL
+ * cfg / d_in / d_out GACQ_ERR_BAD_ARG.  Everything is checked on the host before anything is launched (gacq_mitigate_check makes the
+ * same checks and needs no context); a refused call leaves d_out and d_stats untouched.  n_out = 0 does nothing.  One launch on the
+ * ctx stream, asynchronous.  gacq_mitigate_tile: the output blocks one workgroup of the excision kernel owns (for tests), or
+ * GACQ_ERR_BAD_ARG for a length the kernel does not serve.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gacq_mitigate_cfg {
+  double blank_thr;                /* amplitude threshold of the blanker; 0: blanking off */
+  double ratio;                    /* excision threshold over the frame's median power, > 1 */
+  int hold;                        /* samples blanked on either side of a hit, 0..64 */
+  int nfft;                        /* frame length, a power of two in 64..4096; 0: excision off */
+  int guard;                       /* bins zeroed on either side of a hit bin, 0..8 */
+  int pad;
+} gacq_mitigate_cfg;
+
+int gacq_mitigate_tile(int nfft);
+int gacq_mitigate_check(const gacq_mitigate_cfg* cfg, const void* d_in, int in_complex64, long long in_first, long long in_count,
+                        long long out_first, long long n_out, double gain, int out_complex64, const void* d_out);
+int gacq_mitigate_dev(gacq_ctx* ctx, const gacq_mitigate_cfg* cfg, const void* d_in, int in_complex64, long long in_first, long long in_count,
+                      long long out_first, long long n_out, double gain, int out_complex64, void* d_out, void* d_stats, void* d_frame_bins);
+
+/* ---------------------------------------------------------------------------------------------
  * Navigation data from tracked prompts (gacq_navbits.hip; the framing is host code, gnss_dsp_tools_amd/navdata.py).
  *
  * gacq_navsym: symbol forming and bit synchronisation of K channels, one workgroup per channel.  Everything is host memory: the call
