@@ -213,6 +213,15 @@ SYMBOLS = {
     "gacq_mitigate_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong,
                                          ctypes.c_longlong, ctypes.c_longlong, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p]),
+    # digital down-converter (ddc.py): the gacq_ddc_cfg and the int16 taps as plain addresses
+    "gacq_ddc_tile": (ctypes.c_int, [ctypes.c_int]),
+    "gacq_ddc_table": (ctypes.c_int, [ctypes.c_void_p]),
+    "gacq_ddc_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                                      ctypes.c_longlong, ctypes.c_double, ctypes.c_int]),
+    "gacq_ddc_open": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "gacq_ddc_run_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                                        ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
+    "gacq_ddc_close": (None, [ctypes.c_void_p]),
     # navigation data (navdata.py): host arrays and the gacq_vit_job array as plain addresses
     "gacq_navsym_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

@@ -684,6 +684,50 @@ int gacq_mitigate_dev(gacq_ctx* ctx, const gacq_mitigate_cfg* cfg, const void* d
                       long long out_first, long long n_out, double gain, int out_complex64, void* d_out, void* d_stats, void* d_frame_bins);
 
 /* ---------------------------------------------------------------------------------------------
+ * Digital down-converter (gacq_ddc.hip): a band out of a wide recording.  A mixer, an integer FIR low-pass and integer decimation;
+ * interleaved int8 I/Q in, int8 I/Q or complex64 out.  Output sample m is an exact function of (configuration, gain, absolute sample
+ * index), so the output does not depend on how the recording is cut into calls.  All arithmetic is integer up to the last multiply.
+ * NCO.  dphase = dP = rint(f_shift / fs * 2^64) mod 2^64 (the caller forms it; gnss_dsp_tools_amd/ddc.py does so exactly).  Phase word
+ *     P(n) = (n dP) mod 2^64 of absolute input sample n; table index t(n) = P(n) >> 52; table W[t] = (rint(16384 cos(2 pi t / 4096)),
+ *     rint(16384 sin(2 pi t / 4096))), t < 4096, int16, formed on the host in double (gacq_ddc_table writes the 8192 values, cos first).
+ *     The shift applied is f_act = dP_signed / 2^64 * fs (dP_signed: dP as a signed 64-bit number); a signal at carrier offset c
+ *     appears at c - f_act.
+ * Mixed sample.  x(n) the input as a Gaussian integer, x(n) = 0 for n < 0;  p(n) = x(n) conj(W[t(n)]);  z(n) = (p(n) + 64) >> 7 per
+ *     component, arithmetic shift.  |z| <= 23171 per component: an int16 pair.
+ * Filter and decimation.  Taps g[-H .. H], integers handed over as int32 words (the one-tap filter of a pure shift is g = 32768, one
+ *     more than an int16 holds), T = 2 H + 1 odd in 1..513, sum |g| <= 65536, not required to be symmetric; taps[i] is g[i - H].
+ *     decim = D in 1..64.   acc(m) = sum_{k = -H..H} g[k] z(m D - k)    per component, int32: |acc| < 23171 * 65536 < 2^31,
+ *     exact in any order.  Output m is centred on input m D: no group delay.  The output rate is fs / D.
+ * Output.  v = float32(acc) (round to nearest even); complex64 v * s with s = float32(gain) * 2^-22, one fp32 multiply per component,
+ *     nothing fused (taps that sum to 32768 have unity gain at gain 1); or int8 clip(rint(.), -127, 127) of exactly those values, ties to
+ *     even.
+ * d_in holds input samples in_first .. in_first + in_count - 1; output samples out_first .. out_first + n_out - 1 are written to d_out.
+ * Output m needs inputs m D - H .. m D + H, those below 0 being zero; one that is needed and not present GACQ_ERR_SHORT_INPUT: a
+ * recording of N samples ends at output (N - 1 - H) div D.  D or T out of range, T even, sum |g| > 65536, a gain that is not finite and
+ * positive (as a double and as a float), an index or count below 0 or above 2^48, a NULL pointer, a complex64 d_out off 8 bytes
+ * GACQ_ERR_BAD_ARG.  Everything is checked on the host before the launch; a refused call leaves d_out untouched; n_out = 0 does nothing.
+ * gacq_ddc_open uploads the table and the taps once (it may wait for the device); gacq_ddc_run_dev is one asynchronous launch on the
+ * ctx stream, without synchronisation or state; the handle is closed before its context is destroyed.  gacq_ddc_check makes every
+ * check that needs no pointer to device memory, without a device.  gacq_ddc_tile: the outputs one workgroup owns (for tests), or
+ * GACQ_ERR_BAD_ARG for a D outside 1..64.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gacq_ddc_cfg {
+  unsigned long long dphase;       /* dP: the NCO's phase increment per input sample, in units of 2^-64 cycles */
+  int decim;                       /* D, 1..64 */
+  int pad;
+} gacq_ddc_cfg;
+typedef struct gacq_ddc gacq_ddc;
+
+int gacq_ddc_tile(int decim);
+int gacq_ddc_table(int16_t* table);
+int gacq_ddc_check(const gacq_ddc_cfg* cfg, const int32_t* taps, int T, long long in_first, long long in_count, long long out_first,
+                   long long n_out, double gain, int out_complex64);
+int gacq_ddc_open(gacq_ctx* ctx, const gacq_ddc_cfg* cfg, const int32_t* taps, int T, gacq_ddc** out);
+int gacq_ddc_run_dev(gacq_ddc* h, const void* d_in, long long in_first, long long in_count, long long out_first, long long n_out, double gain,
+                     int out_complex64, void* d_out);
+void gacq_ddc_close(gacq_ddc* h);
+
+/* ---------------------------------------------------------------------------------------------
  * Navigation data from tracked prompts (gacq_navbits.hip; the framing is host code, gnss_dsp_tools_amd/navdata.py).
  *
  * gacq_navsym: symbol forming and bit synchronisation of K channels, one workgroup per channel.  Everything is host memory: the call
