@@ -222,6 +222,14 @@ SYMBOLS = {
     "gacq_ddc_run_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                         ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
     "gacq_ddc_close": (None, [ctypes.c_void_p]),
+    # level control and requantiser (requant.py): the gacq_requant_cfg, the float32 gains and the uint64 thresholds as plain addresses
+    "gacq_requant_tile": (ctypes.c_int, [ctypes.c_void_p]),
+    "gacq_requant_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                                          ctypes.c_longlong]),
+    "gacq_requant_open": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "gacq_requant_run_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gacq_requant_close": (None, [ctypes.c_void_p]),
     # navigation data (navdata.py): host arrays and the gacq_vit_job array as plain addresses
     "gacq_navsym_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

@@ -728,6 +728,63 @@ int gacq_ddc_run_dev(gacq_ddc* h, const void* d_in, long long in_first, long lon
 void gacq_ddc_close(gacq_ddc* h);
 
 /* ---------------------------------------------------------------------------------------------
+ * Level control and requantiser (gacq_requant.hip): the inverse of ingest.  Interleaved integer I/Q in, any ingest container out,
+ * under a gain that follows the block power of the recording.  Every decision is an integer function of the absolute block index, so
+ * the bytes do not depend on how the recording is cut into calls.
+ * Input.  x(j), j >= 0: interleaved I/Q, in_bits = 8 (int8) or 16 (little-endian int16, d_in 2-byte aligned).
+ * 1. Block power.  block = Lb, a multiple of 16 in 16..65536; block b covers samples b Lb .. (b + 1) Lb - 1.
+ *    P(b) = sum re^2 + im^2 over the block, an exact unsigned 64-bit integer (P(b) <= Lb 2^31).
+ * 2. Level.  window = W in 1..64.  S(b) = P(b - W) + .. + P(b - 1) for b >= W; S(b) = P(0) + .. + P(W - 1) for b < W (the warm-up).
+ *    S(b) <= 2^53.  Causal and not recursive: a function of b alone.
+ * 3. Gain.  ngains = K in 1..256; gains G[0 .. K-1], float32, each finite and positive; thresholds T[0] <= T[1] <= .. <= T[K-2],
+ *    unsigned 64-bit (host arrays; thresholds may be NULL when K = 1).  k(b) = the number of i with S(b) > T[i] (strict), g(b) = G[k(b)].
+ *    The library forms no table: it checks order and finiteness only.  K = 1 is a fixed gain.
+ * 4. Value.  v = float32(component) * g(j div Lb): one fp32 multiply per component, nothing fused.
+ * 5. Output container (the GACQ_INGEST_* numbers):
+ *     S8      clip(rint(v), -127, 127), ties to even: the canonical int8;     U8   that value plus 128;
+ *     S16     clip(rint(v), -32767, 32767), little-endian (d_out 2-byte aligned);     F32  v itself, complex64 (d_out 8-byte aligned);
+ *     PACKED  bits in {1, 2, 4}, n = 2^bits: level index q = clip(floor(v * 0.5f) + n/2, 0, n - 1), which stands for the odd integer
+ *             2q - (n - 1) (v in [0, 2) gives +1); code enc[q], enc a permutation of 0 .. n-1; codes in the order I0, Q0, I1, Q1, ..,
+ *             8 / bits to a byte, code i of a byte at bit 8 - bits (i + 1) with msb_first, at bits i without: ingest's positions.
+ *             out_first and n_out are multiples of the samples per byte, 4 / bits.
+ * 6. Statistics.  d_stats (NULL, or two uint64 that the caller zeroed, 8-byte aligned; added to with vector integer atomics):
+ *    [0] the components of the output range that the clip changed (PACKED: q clipped; F32: none); [1] the owned blocks, those with
+ *    out_first <= b Lb < out_first + n_out.  d_gain_index (NULL, or one uint8 k(b) per owned block, in block order).  The totals of any
+ *    partition of the outputs into calls sum to those of one call.
+ * d_in holds input samples in_first .. in_first + in_count - 1; output samples out_first .. out_first + n_out - 1 are written to d_out.
+ * Output j in block b needs input j and inputs max(b - W, 0) Lb .. max(b, W) Lb - 1; one that is needed and not present
+ * GACQ_ERR_SHORT_INPUT: a recording shorter than W blocks gives no output, and the last partial block is produced.  A value outside
+ * the ranges above, an unknown container, enc not a permutation, T not ascending, a gain that is not finite and positive, an index or
+ * count below 0 or above 2^48, a misaligned int16 or complex64 buffer or d_stats, a NULL pointer GACQ_ERR_BAD_ARG.  Everything is
+ * checked on the host before anything is launched; a refused call leaves d_out and d_stats untouched; n_out = 0 does nothing.
+ * gacq_requant_check makes every check that needs no device pointer, without a context.  gacq_requant_open uploads the tables once
+ * and allocates the handle's workspace (it may wait for the device); gacq_requant_run_dev is two launches (block powers, then the
+ * outputs) per 2^16 blocks on the ctx stream, asynchronous, without state between calls: calls on one handle are ordered by that
+ * stream.  The handle is closed before its context is destroyed.  gacq_requant_tile: the outputs one workgroup owns (for tests), or
+ * GACQ_ERR_BAD_ARG.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gacq_requant_cfg {
+  int in_bits;                     /* 8: int8 input; 16: little-endian int16 */
+  int container;                   /* output: GACQ_INGEST_* */
+  int bits;                        /* PACKED: bits per code, 1, 2 or 4 */
+  int msb_first;                   /* PACKED: the first code of a byte is in its top bits */
+  int block;                       /* Lb: samples per power block, a multiple of 16 in 16..65536 */
+  int window;                      /* W: blocks the level sums over, 1..64 */
+  int ngains;                      /* K: entries of the gain table, 1..256 */
+  int pad;
+  uint8_t enc[16];                 /* PACKED: code of each level index, a permutation of 0 .. 2^bits - 1 */
+} gacq_requant_cfg;
+typedef struct gacq_requant gacq_requant;
+
+int gacq_requant_tile(const gacq_requant_cfg* cfg);
+int gacq_requant_check(const gacq_requant_cfg* cfg, const float* gains, const uint64_t* thresholds, long long in_first, long long in_count,
+                       long long out_first, long long n_out);
+int gacq_requant_open(gacq_ctx* ctx, const gacq_requant_cfg* cfg, const float* gains, const uint64_t* thresholds, gacq_requant** out);
+int gacq_requant_run_dev(gacq_requant* h, const void* d_in, long long in_first, long long in_count, long long out_first, long long n_out,
+                         void* d_out, void* d_stats, void* d_gain_index);
+void gacq_requant_close(gacq_requant* h);
+
+/* ---------------------------------------------------------------------------------------------
  * Navigation data from tracked prompts (gacq_navbits.hip; the framing is host code, gnss_dsp_tools_amd/navdata.py).
  *
  * gacq_navsym: symbol forming and bit synchronisation of K channels, one workgroup per channel.  Everything is host memory: the call
