@@ -230,6 +230,12 @@ SYMBOLS = {
     "gacq_requant_run_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gacq_requant_close": (None, [ctypes.c_void_p]),
+    # cancellation of tracked signals (cancel.py): the gacq_cancel_sat and gacq_cancel_seg arrays as plain addresses
+    "gacq_cancel_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                         ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]),
+    "gacq_cancel_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_void_p,
+                                       ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     # navigation data (navdata.py): host arrays and the gacq_vit_job array as plain addresses
     "gacq_navsym_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

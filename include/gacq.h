@@ -785,6 +785,65 @@ int gacq_requant_run_dev(gacq_requant* h, const void* d_in, long long in_first, 
 void gacq_requant_close(gacq_requant* h);
 
 /* ---------------------------------------------------------------------------------------------
+ * Cancellation of tracked signals (gacq_cancel.hip): rebuild known spread-spectrum signals from per-segment parameters and take them
+ * out of a recording, interleaved int8 I/Q (in_complex64 = 0) or complex64 in, int8 I/Q or complex64 out.  Output sample j is a
+ * function of (segments, amplitudes, x(j), j) only: the same bytes however a caller cuts the recording into calls and wherever d_in and
+ * d_out lie.
+ * A satellite is (code, prn, kind) as in gacq_sim_sat, followed by the number of its segments; segs holds the segments of satellite 0,
+ * then those of satellite 1, and so on.  A segment says how its satellite's signal runs over samples s0 .. s0 + n - 1 of the recording
+ * (absolute indices).  The doubles become fixed point once on the host, by the rules of gacq_simulate_dev:
+ *     F = floor(frac(carrier_hz / fs) 2^64), p0 = floor(frac(carrier_phase) 2^64)   (carrier_phase: turns at s0)
+ *     Cf = floor((code_rate_hz / fs) 2^64),  c0 = floor(code_phase 2^64)            (code_phase: chips at s0, in [0, L))
+ * and for i = j - s0
+ *     theta(j) = (p0 + i F) mod 2^64,   pos(j) = c0 + i Cf   (exact integer: chip (pos >> 64) mod L, subchip fraction pos mod 2^64)
+ *     r(j) = w(pos(j)) exp(2 pi i theta(j) / 2^64)           (w: simulate's chip weight of `kind` at unit amplitude, no symbols)
+ * The segments of one satellite ascend in s0 and do not overlap; nothing of a satellite is subtracted in a gap between its segments.
+ * Estimate (estimate != 0).  For every segment that touches the output range:
+ *     C = sum_j x(j) conj(r(j)),   E = sum_j w(pos(j))^2,   A = C / E (0 when E = 0)
+ *   with fp32 products (w cos, w sin; re = xr rr + xi ri, im = xi rr - xr ri; w w; each product and sum rounded on its own) and fp64 sums
+ *   in an order that depends on i alone: the bits of A are a function of the segment and its own samples, not of the call, the other
+ *   segments or the addresses.  Every amplitude is estimated on the input, never on a partly cancelled signal (parallel cancellation).
+ *   Without the flag A = (amp_re, amp_im).
+ * Subtract.  v(j) = x(j) - sum_k float32(A_k) r_k(j) in fp32, one satellite after the other in ascending k, over the satellites that
+ *   have a segment covering j.
+ * d_out (device): complex64 v (out_complex64 != 0, 8-byte aligned), or interleaved int8 clip(rint(v), -127, 127) with ties to even, of
+ * the very values the complex64 form holds.  The int8 rule is applied to every sample, covered or not: an input of -128 comes out as
+ * -127.  d_in holds input samples in_first .. in_first + in_count - 1; outputs out_first .. out_first + n_out - 1 are written.
+ * amps_out (host, NULL or one complex128 per segment): A of every segment that touches the output range; the other entries are left as
+ * they are.  clipped (host, NULL or one count): the components of an int8 output that are +127 or -127 (0 for complex64 output).
+ * Limits: K in 1..32, at most 2^20 segments, n in 1..2^24, codes of at most 10240 chips, indices and counts at most 2^48.
+ * Checked on the host before anything is allocated or launched (gacq_cancel_check makes the same checks and needs no context): a value
+ * that is not finite, fs <= 0, code_rate_hz <= 0 or code_rate_hz / fs >= 16, code_phase outside [0, L), kind outside 0..5, K, a segment
+ * count, n, an index or a count out of range, overlapping or unsorted segments, a complex64 buffer off 8 bytes, a NULL pointer
+ * GACQ_ERR_BAD_ARG; an unknown code or PRN GACQ_ERR_UNKNOWN_CODE / GACQ_ERR_BAD_PRN; a code longer than 10240 chips
+ * GACQ_ERR_UNSUPPORTED; an output sample whose input is not present, or with estimate a segment that touches the output range and does
+ * not lie wholly inside the input, GACQ_ERR_SHORT_INPUT.  A refused call leaves d_out untouched; n_out = 0 does nothing.  Up to two
+ * launches on the ctx stream; the call returns when the results are there.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gacq_cancel_sat {
+  const char* code;                /* code module, e.g. "gps.ca" */
+  int prn;                         /* PRN (GLONASS: 0) */
+  int kind;                        /* chip weight, 0 plain .. 5 RZ [0,1] */
+  int nseg;                        /* segments of this satellite in segs, >= 0 */
+  int pad;
+} gacq_cancel_sat;
+typedef struct gacq_cancel_seg {
+  long long s0;                    /* first sample (absolute index) */
+  long long n;                     /* samples, 1..2^24 */
+  double carrier_hz;               /* carrier frequency in the recording, Hz */
+  double carrier_phase;            /* carrier phase at s0, turns */
+  double code_rate_hz;             /* chips per second */
+  double code_phase;               /* code phase at s0, chips, in [0, L) */
+  double amp_re, amp_im;           /* complex amplitude (used when estimate = 0) */
+} gacq_cancel_seg;
+
+int gacq_cancel_check(const gacq_cancel_sat* sats, int K, const gacq_cancel_seg* segs, double fs, int estimate, const void* d_in, int in_complex64,
+                      long long in_first, long long in_count, long long out_first, long long n_out, int out_complex64, const void* d_out);
+int gacq_cancel_dev(gacq_ctx* ctx, const gacq_cancel_sat* sats, int K, const gacq_cancel_seg* segs, double fs, int estimate, const void* d_in,
+                    int in_complex64, long long in_first, long long in_count, long long out_first, long long n_out, int out_complex64, void* d_out,
+                    double* amps_out, unsigned long long* clipped);
+
+/* ---------------------------------------------------------------------------------------------
  * Navigation data from tracked prompts (gacq_navbits.hip; the framing is host code, gnss_dsp_tools_amd/navdata.py).
  *
  * gacq_navsym: symbol forming and bit synchronisation of K channels, one workgroup per channel.  Everything is host memory: the call
