@@ -1,0 +1,482 @@
+// Spatial nulling with an antenna array (gacq_null_*, include/gacq.h): M int8 I/Q recordings on one clock in, one recording out, under
+// block-wise weights that minimise the output power subject to one linear constraint.  The covariances are exact integers and the
+// solve is one written-out fp64 sequence, so every output byte is a function of (configuration, absolute sample index) alone.
+//
+// Three launches per call (per 2^14 blocks), on one stream:
+//   null_cov_kernel      C_b of every block the call's weights need, into the handle's workspace.  The spatial covariance of M complex
+//      antennas is the Gram matrix of 2M real rows (I_0, Q_0, I_1, ..), rows from 2M up zero: one 16 x 16 x 64 int8 matrix instruction
+//      per 64 samples, accumulated in int32.  Lane l holds row l & 15 at samples 16 (l >> 4) .. + 15 of the group: two 16-byte loads
+//      at any address (lanes 2p and 2p + 1 load the same 32 bytes), the I or the Q bytes picked with four byte permutes.  The product is
+//      G = A A^T, and the B fragment of lane l (column l & 15, k-group l >> 4) holds the bytes of its A fragment: the same four registers
+//      are both operands, so the result does not depend on the order of k inside a fragment, and rows I_p and Q_p see sample j at the
+//      same k because both take their bytes with the same permute pattern.  min(4, Lb / 64) waves share a block (4, 2 or 1 blocks a
+//      workgroup), their partial tiles meet in LDS; the lane that holds column 2q takes column 2q + 1 from its neighbour and writes
+//      Re C = G[2p][2q] + G[2p+1][2q+1], Im C = G[2p+1][2q] - G[2p][2q+1] -- no negated row, -(-128) does not fit int8.
+//   null_weights_kernel  a wave per block, lane 8 r + c holds A[r][c]: the window sum in int64, the loading, Gaussian elimination and back
+//      substitution in the order of the header, the pivot row, the multiplier and the partial products fetched from their lanes;
+//      every lane runs the same fp64 sequence as tests/nulling_oracle.py.  No per-lane array: nothing goes to scratch.
+//   null_apply_kernel    a lane's run is the 8 samples at a multiple of 8 of the ABSOLUTE sample index, so a run lies in one block
+//      (Lb is a multiple of 64) whatever out_first is: M 16-byte loads, 24-bit integer multiply-adds, one 16-byte store (int8) or four
+//      (complex64).  A workgroup owns the 16384 samples at a multiple of 16384 (run r of a lane is run 256 r + lane of the tile); only
+//      the runs over the ends of the output range work sample by sample.  The weights of a run's block come from the workspace (the
+//      lanes of a wave read the same 64 bytes).
+#pragma clang fp contract(off)
+
+#include "gacq_common.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+using namespace gacq;
+
+namespace {
+
+constexpr int kNlBlock = 256;
+constexpr int kNlMaxM = 8, kNlMaxWindow = 64, kNlMaxLb = 32768, kNlMaxShift = 40;
+constexpr long long kNlMaxIndex = 1ll << 48;
+constexpr long long kNlChunkBlocks = 1ll << 14;      // blocks whose outputs one triple of launches writes, at most (2^29 samples)
+constexpr int kNlRuns = 8;                           // runs a lane works through
+constexpr int kNlTile = kNlBlock * kNlRuns * 8;      // 16384 samples a workgroup
+constexpr unsigned kNlMaxGrid = 1u << 16;            // workgroups; a longer call loops
+constexpr int kNlWq = 1 << 14;                       // weight scale 2^14
+constexpr int kNlWqMax = 131071;
+
+typedef int nl_v4i __attribute__((ext_vector_type(4)));
+
+// 16 bytes at any address: a byte-aligned copy, for which the compiler emits one wide load
+__device__ __forceinline__ uint4 nl_load16(const uint8_t* p) {
+  uint4 v;
+  __builtin_memcpy(&v, p, 16);
+  return v;
+}
+
+// ---- block covariances
+
+struct NlCovArgs {
+  const uint8_t* in[kNlMaxM];   // antenna p: the address of the first sample of block 0 of the launch
+  int* C;                       // [block][8][8][2]
+  long long nblk;
+  int Lb, M;
+  int wpb_log2;                 // waves per block: 1, 2 or 4
+};
+
+// two workgroups a compute unit at the least: with at most 256 registers a wave the compiler keeps the matrix instruction's
+// accumulator in VGPRs (with all 512 in reach it takes accumulator registers)
+__global__ __launch_bounds__(kNlBlock, 2) void null_cov_kernel(const NlCovArgs a) {
+  __shared__ int red[kNlBlock / 64][4][64];
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int row = lane & 15, kg = lane >> 4, p = row >> 1;
+  const unsigned sel = (row & 1) ? 0x07050301u : 0x06040200u;           // bytes 1, 3 (Q) or 0, 2 (I) of two dwords
+  const uint8_t* src = a.in[0];
+#pragma unroll
+  for (int q = 1; q < kNlMaxM; q++)
+    if (p == q && q < a.M) src = a.in[q];
+  const bool live = p < a.M;
+  const int wpb = 1 << a.wpb_log2, per = (kNlBlock / 64) >> a.wpb_log2;
+  const int blw = wave >> a.wpb_log2, sub = wave & (wpb - 1);
+  const int groups = a.Lb >> 6;
+  const long long npass = (a.nblk + per - 1) / per;
+  for (long long pass = blockIdx.x; pass < npass; pass += gridDim.x) {
+    const long long bl = pass * per + blw;
+    nl_v4i acc = {0, 0, 0, 0};
+    if (bl < a.nblk) {
+      const uint8_t* pb = src + (bl * a.Lb + 16 * kg) * 2;
+      for (int g = sub; g < groups; g += wpb) {
+        nl_v4i f = {0, 0, 0, 0};
+        if (live) {
+          const uint4 lo = nl_load16(pb + 128 * (long long)g), hi = nl_load16(pb + 128 * (long long)g + 16);
+          f.x = (int)__builtin_amdgcn_perm(lo.y, lo.x, sel);
+          f.y = (int)__builtin_amdgcn_perm(lo.w, lo.z, sel);
+          f.z = (int)__builtin_amdgcn_perm(hi.y, hi.x, sel);
+          f.w = (int)__builtin_amdgcn_perm(hi.w, hi.z, sel);
+        }
+        acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(f, f, acc, 0, 0, 0);
+      }
+    }
+    red[wave][0][lane] = acc.x;
+    red[wave][1][lane] = acc.y;
+    red[wave][2][lane] = acc.z;
+    red[wave][3][lane] = acc.w;
+    __syncthreads();
+    if (sub == 0 && bl < a.nblk) {
+      // the lane holds G[4 kg + i][lane & 15], i < 4: rows I, Q of antenna 2 kg and I, Q of antenna 2 kg + 1
+      int g[4], n[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        g[i] = 0;
+        for (int s = 0; s < wpb; s++) g[i] += red[wave + s][i][lane];
+        n[i] = __shfl_xor(g[i], 1, 64);                                 // the same rows of the neighbouring column
+      }
+      if (!(lane & 1)) {
+        const int q = (lane & 15) >> 1;
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          int* o = a.C + ((bl * 8 + 2 * kg + h) * 8 + q) * 2;
+          *reinterpret_cast<int2*>(o) = make_int2(g[2 * h] + n[2 * h + 1], g[2 * h + 1] - n[2 * h]);
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ---- weights
+
+struct NlWgtArgs {
+  const int* C;                 // C[i] is block pb0 + i
+  int* Wq;                      // [block][8][2]: the launch's block i at Wq[16 i]
+  long long* cov;               // d_cov, or NULL
+  int* wout;                    // d_weights, or NULL
+  double c[2 * kNlMaxM];
+  long long b_first;            // the absolute index of the launch's block 0
+  long long own_first;          // the call's first owned block
+  int nblk;
+  int p_off;                    // b_first less the block of C[0]
+  int warm;                     // blocks b_first + i with i < warm are in the warm-up: their window is C[0 .. W - 1]
+  int W, M, shift;
+};
+
+__device__ __forceinline__ int nl_quantise(double w) {
+  const double s = w * (double)kNlWq;
+  if (!__builtin_isfinite(s)) return 0;
+  return (int)fmin(fmax(rint(s), -(double)kNlWqMax), (double)kNlWqMax);
+}
+
+__global__ __launch_bounds__(kNlBlock) void null_weights_kernel(const NlWgtArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * (kNlBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (i >= a.nblk) return;
+  const int r = lane >> 3, c = lane & 7, M = a.M;
+  const bool in = r < M && c < M;
+  // ---- the window sum
+  const int* pc = a.C + ((long long)(i >= a.warm ? a.p_off + i - a.W : 0) * 64 + lane) * 2;
+  long long Rre = 0, Rim = 0;
+  for (int j = 0; j < a.W; j++) {
+    const int2 v = *reinterpret_cast<const int2*>(pc + 128 * (long long)j);
+    Rre += v.x;
+    Rim += v.y;
+  }
+  const long long b = a.b_first + i;
+  const bool owned = b >= a.own_first;
+  if (owned && a.cov && in) {
+    long long* o = a.cov + (((b - a.own_first) * M + r) * M + c) * 2;
+    o[0] = Rre;
+    o[1] = Rim;
+  }
+  // ---- the loading
+  long long t = 0;
+  for (int p = 0; p < M; p++) t += __shfl(Rre, 9 * p, 64);
+  const long long d = (t >> a.shift) + 1;
+  double Are = in ? (double)(Rre + (r == c ? d : 0)) : 0.0, Aim = in ? (double)Rim : 0.0;
+  double cre = 0.0, cim = 0.0, bre = 0.0, bim = 0.0;                    // c of the lane's column, b of its row
+#pragma unroll
+  for (int q = 0; q < kNlMaxM; q++) {
+    if (c == q && q < M) cre = a.c[2 * q], cim = a.c[2 * q + 1];
+    if (r == q && q < M) bre = a.c[2 * q], bim = a.c[2 * q + 1];
+  }
+  // ---- elimination: A[r][c] -= m A[k][c], b[r] -= m b[k] with m = A[r][k] / piv, for r > k
+  for (int k = 0; k < M; k++) {
+    const double piv = __shfl(Are, 9 * k, 64);
+    const double lre = __shfl(Are, 8 * r + k, 64), lim = __shfl(Aim, 8 * r + k, 64);
+    const double ure = __shfl(Are, 8 * k + c, 64), uim = __shfl(Aim, 8 * k + c, 64);
+    const double kre = __shfl(bre, 8 * k, 64), kim = __shfl(bim, 8 * k, 64);
+    if (r > k && r < M) {
+      const double mre = lre / piv, mim = lim / piv;
+      if (c > k && c < M) {
+        Are = Are - (mre * ure - mim * uim);
+        Aim = Aim - (mre * uim + mim * ure);
+      }
+      bre = bre - (mre * kre - mim * kim);
+      bim = bim - (mre * kim + mim * kre);
+    }
+  }
+  // ---- back substitution: the lane keeps u of its column
+  double ucr = 0.0, uci = 0.0;
+  for (int k = M - 1; k >= 0; k--) {
+    const double pre = Are * ucr - Aim * uci, pim = Are * uci + Aim * ucr;      // A[r][c] u[c]
+    double sre = __shfl(bre, 8 * k, 64), sim = __shfl(bim, 8 * k, 64);
+    for (int q = k + 1; q < M; q++) {
+      sre = sre - __shfl(pre, 8 * k + q, 64);
+      sim = sim - __shfl(pim, 8 * k + q, 64);
+    }
+    const double piv = __shfl(Are, 9 * k, 64);
+    const double xr = sre / piv, xi = sim / piv;
+    if (c == k) ucr = xr, uci = xi;
+  }
+  // ---- the constraint's scale
+  const double tp = cre * ucr + cim * uci;
+  double den = __shfl(tp, 0, 64);
+  for (int p = 1; p < M; p++) den = den + __shfl(tp, p, 64);
+  const int qr = c < M ? nl_quantise(ucr / den) : 0, qi = c < M ? nl_quantise(uci / den) : 0;
+  if (r == 0) {
+    *reinterpret_cast<int2*>(a.Wq + 16 * (long long)i + 2 * c) = make_int2(qr, qi);
+    if (owned && a.wout && c < M) {
+      int* o = a.wout + ((b - a.own_first) * M + c) * 2;
+      o[0] = qr;
+      o[1] = qi;
+    }
+  }
+}
+
+// ---- outputs
+
+struct NlApplyArgs {
+  const uint8_t* in[kNlMaxM];   // antenna p: the address of input sample j0
+  uint8_t* out;                 // the address of output sample j0
+  const int* Wq;                // the weights of block b_first + i at Wq[16 i]
+  unsigned long long* stats;
+  long long j0, n;              // the launch's outputs: absolute samples j0 .. j0 + n - 1
+  long long blk0;               // the first sample of block b_first (<= j0)
+  unsigned long long owned;     // what the launch adds to stats[1]
+  float s;
+  int Lb, M;
+};
+
+template <bool F32>
+__global__ __launch_bounds__(kNlBlock) void null_apply_kernel(const NlApplyArgs a) {
+  const int tid = threadIdx.x;
+  const long long t0 = a.j0 / kNlTile, j_end = a.j0 + a.n;
+  const long long ntiles = (j_end - 1) / kNlTile - t0 + 1;
+  unsigned nclip = 0;
+  for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+#pragma unroll 1
+    for (int rr = 0; rr < kNlRuns; rr++) {
+      const long long j = (t0 + tile) * kNlTile + (rr * kNlBlock + tid) * 8;
+      if (j + 8 <= a.j0 || j >= j_end) continue;
+      const bool full = j >= a.j0 && j + 8 <= j_end;
+      const int* w = a.Wq + 16 * (long long)((unsigned)(j - a.blk0) / (unsigned)a.Lb);
+      int yr[8], yi[8];
+#pragma unroll
+      for (int e = 0; e < 8; e++) yr[e] = yi[e] = 0;
+#pragma unroll
+      for (int p = 0; p < kNlMaxM; p++) {
+        if (p < a.M) {
+          const int2 wq = *reinterpret_cast<const int2*>(w + 2 * p);
+          const uint8_t* ps = a.in[p] + (j - a.j0) * 2;
+          unsigned x[4];
+          if (full) {
+            __builtin_memcpy(x, ps, 16);
+          } else {
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+              unsigned v = 0u;
+              if (j + e >= a.j0 && j + e < j_end) v = (unsigned)ps[2 * e] | ((unsigned)ps[2 * e + 1] << 8);
+              if (e & 1) x[e >> 1] |= v << 16;
+              else x[e >> 1] = v;
+            }
+          }
+#pragma unroll
+          for (int e = 0; e < 8; e++) {
+            const int xr = (int)(signed char)(unsigned char)(x[e >> 1] >> (16 * (e & 1)));
+            const int xi = (int)(signed char)(unsigned char)(x[e >> 1] >> (16 * (e & 1) + 8));
+            yr[e] += __mul24(wq.x, xr) + __mul24(wq.y, xi);
+            yi[e] += __mul24(wq.x, xi) - __mul24(wq.y, xr);
+          }
+        }
+      }
+      if constexpr (F32) {
+        float o[16];
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          o[2 * e] = (float)yr[e] * a.s;
+          o[2 * e + 1] = (float)yi[e] * a.s;
+        }
+        float* po = reinterpret_cast<float*>(a.out) + (j - a.j0) * 2;
+        if (full) {
+          __builtin_memcpy(reinterpret_cast<uint8_t*>(po), o, 64);      // four 16-byte stores; the output lies on 8 bytes
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; e++)
+            if (j + e >= a.j0 && j + e < j_end) *reinterpret_cast<float2*>(po + 2 * e) = make_float2(o[2 * e], o[2 * e + 1]);
+        }
+      } else {
+        unsigned q[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+          const float v = (float)((e & 1) ? yi[e >> 1] : yr[e >> 1]) * a.s;     // a sample outside the range is 0 here: it clips nothing
+          const float rv = rintf(v);                                    // half to even
+          const float cv = fminf(fmaxf(rv, -127.0f), 127.0f);
+          nclip += cv != rv ? 1u : 0u;
+          q[e >> 2] |= ((unsigned)(int)cv & 0xffu) << (8 * (e & 3));
+        }
+        uint8_t* po = a.out + (j - a.j0) * 2;
+        if (full) {
+          __builtin_memcpy(po, q, 16);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 16; e++)
+            if (j + (e >> 1) >= a.j0 && j + (e >> 1) < j_end) po[e] = (uint8_t)(q[e >> 2] >> (8 * (e & 3)));
+        }
+      }
+    }
+  }
+  if (a.stats) {
+    if (!F32) {
+      for (int off = 1; off < 64; off <<= 1) nclip += __shfl_xor(nclip, off, 64);
+      if ((tid & 63) == 0 && nclip) atomicAdd(a.stats, (unsigned long long)nclip);
+    }
+    if (blockIdx.x == 0 && tid == 0 && a.owned) atomicAdd(a.stats + 1, a.owned);
+  }
+}
+
+int check_cfg(const gacq_null_cfg* c) {
+  if (!c) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: NULL argument");
+  if (c->antennas < 2 || c->antennas > kNlMaxM)
+    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: %d antennas: need 2..%d", c->antennas, kNlMaxM);
+  if (c->block < 64 || c->block > kNlMaxLb || c->block % 64)
+    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: the block length %d is no multiple of 64 in 64..%d", c->block, kNlMaxLb);
+  if (c->window < 1 || c->window > kNlMaxWindow)
+    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: the window %d lies outside 1..%d", c->window, kNlMaxWindow);
+  if (c->load_shift < 0 || c->load_shift > kNlMaxShift)
+    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: load_shift %d lies outside 0..%d", c->load_shift, kNlMaxShift);
+  bool any = false;
+  for (int i = 0; i < 2 * c->antennas; i++) {
+    if (!std::isfinite(c->c[i])) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: constraint component %d is not finite", i);
+    any = any || c->c[i] != 0.0;
+  }
+  if (!any) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: the constraint is all zero");
+  return GACQ_OK;
+}
+
+}  // namespace
+
+struct gacq_null {
+  gacq_ctx* ctx = nullptr;
+  gacq_null_cfg cfg{};
+  void* dev = nullptr;          // the block covariances of a triple of launches, then the weights of its blocks
+};
+
+extern "C" int gacq_null_tile(const gacq_null_cfg* cfg) {
+  if (!cfg || check_cfg(cfg) < 0) return GACQ_ERR_BAD_ARG;
+  return kNlTile;
+}
+
+extern "C" int gacq_null_check(const gacq_null_cfg* cfg, long long in_first, long long in_count, long long out_first, long long n_out, double gain,
+                               int out_complex64) {
+  const int rc = check_cfg(cfg);
+  if (rc < 0) return rc;
+  (void)out_complex64;                                                  // either form takes every range
+  if (!std::isfinite(gain) || !(gain > 0.0) || !std::isfinite((float)gain) || !((float)gain > 0.0f))
+    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: the gain is not finite and positive (%g)", gain);
+  if (in_first < 0 || in_count < 0 || out_first < 0 || n_out < 0 || in_first > kNlMaxIndex || in_count > kNlMaxIndex || out_first > kNlMaxIndex ||
+      n_out > kNlMaxIndex)
+    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: need 0 <= in_first, in_count, out_first, n_out <= 2^48 (%lld, %lld, %lld, %lld)", in_first,
+                     in_count, out_first, n_out);
+  if (n_out == 0) return GACQ_OK;
+  const long long Lb = cfg->block, W = cfg->window, b_lo = out_first / Lb;
+  const long long need_lo = std::max(b_lo - W, 0ll) * Lb, need_hi = std::max(out_first + n_out, W * Lb) - 1;
+  if (need_lo < in_first || need_hi >= in_first + in_count)
+    return set_error(nullptr, GACQ_ERR_SHORT_INPUT, "gacq_null: outputs %lld .. %lld need input samples %lld .. %lld, present are %lld .. %lld", out_first,
+                     out_first + n_out - 1, need_lo, need_hi, in_first, in_first + in_count - 1);
+  return GACQ_OK;
+}
+
+extern "C" int gacq_null_open(gacq_ctx* ctx, const gacq_null_cfg* cfg, gacq_null** out) {
+  if (!ctx) return GACQ_ERR_BAD_ARG;
+  if (!out) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_open: NULL argument");
+  *out = nullptr;
+  const int rc = gacq_null_check(cfg, 0, 0, 0, 0, 1.0, 0);
+  if (rc < 0) return set_error(ctx, rc, "%s", gacq_last_error(nullptr));
+  gacq_null* h = new gacq_null;
+  h->ctx = ctx;
+  h->cfg = *cfg;
+  {
+    GACQ_DEVICE(ctx);
+    const hipError_t e = hipMalloc(&h->dev, ((size_t)(kNlChunkBlocks + kNlMaxWindow) * 128 + (size_t)kNlChunkBlocks * 16) * sizeof(int));
+    if (e != hipSuccess) {
+      delete h;
+      return set_error(ctx, GACQ_ERR_HIP, "gacq_null_open: %s", hipGetErrorString(e));
+    }
+  }
+  *out = h;
+  return GACQ_OK;
+}
+
+extern "C" void gacq_null_close(gacq_null* h) {
+  if (!h) return;
+  if (h->dev) {
+    DeviceGuard guard(h->ctx->device);
+    (void)hipFree(h->dev);
+  }
+  delete h;
+}
+
+extern "C" int gacq_null_run_dev(gacq_null* h, const void* const* d_in, long long in_first, long long in_count, long long out_first, long long n_out,
+                                 double gain, int out_complex64, void* d_out, void* d_stats, void* d_weights, void* d_cov) {
+  if (!h) return GACQ_ERR_BAD_ARG;
+  gacq_ctx* ctx = h->ctx;
+  const gacq_null_cfg& c = h->cfg;
+  if (!d_in || !d_out) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: NULL argument");
+  for (int p = 0; p < c.antennas; p++)
+    if (!d_in[p]) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: the pointer of antenna %d is NULL", p);
+  // everything is checked before anything is launched
+  const int rc = gacq_null_check(&c, in_first, in_count, out_first, n_out, gain, out_complex64);
+  if (rc < 0) return set_error(ctx, rc, "%s", gacq_last_error(nullptr));
+  if (out_complex64 && (uintptr_t)d_out % 8u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: complex64 output must be 8-byte aligned");
+  if ((uintptr_t)d_stats % 8u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: d_stats must be 8-byte aligned");
+  if ((uintptr_t)d_weights % 4u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: d_weights must be 4-byte aligned");
+  if ((uintptr_t)d_cov % 8u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: d_cov must be 8-byte aligned");
+  if (n_out == 0) return GACQ_OK;
+  const int M = c.antennas;
+  const long long Lb = c.block, W = c.window, out_end = out_first + n_out;
+  const long long own_first = (out_first + Lb - 1) / Lb;
+  int* dC = (int*)h->dev;
+  int* dWq = dC + (size_t)(kNlChunkBlocks + kNlMaxWindow) * 128;
+  GACQ_DEVICE(ctx);
+  for (long long o = out_first; o < out_end;) {
+    const long long b0 = o / Lb, o_end = std::min(out_end, (b0 + kNlChunkBlocks) * Lb), b_hi = (o_end - 1) / Lb;
+    // ---- the covariances the weights of blocks b0 .. b_hi need
+    NlCovArgs cv;
+    const long long pb0 = std::max(b0 - W, 0ll);
+    for (int p = 0; p < kNlMaxM; p++) cv.in[p] = (const uint8_t*)d_in[p < M ? p : 0] + (pb0 * Lb - in_first) * 2;
+    cv.C = dC;
+    cv.nblk = std::max(b_hi, W) - pb0;
+    cv.Lb = (int)Lb;
+    cv.M = M;
+    cv.wpb_log2 = Lb >= 256 ? 2 : Lb >= 128 ? 1 : 0;
+    const long long per = (kNlBlock / 64) >> cv.wpb_log2, npass = (cv.nblk + per - 1) / per;
+    hipLaunchKernelGGL(null_cov_kernel, dim3((unsigned)std::min<long long>(npass, (long long)kNlMaxGrid)), dim3(kNlBlock), 0, ctx->stream, cv);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_null_run_dev: launch failed: %s", hipGetErrorString(e));
+    // ---- the weights of blocks b0 .. b_hi
+    NlWgtArgs wg;
+    wg.C = dC;
+    wg.Wq = dWq;
+    wg.cov = (long long*)d_cov;
+    wg.wout = (int*)d_weights;
+    for (int i = 0; i < 2 * kNlMaxM; i++) wg.c[i] = i < 2 * M ? c.c[i] : 0.0;
+    wg.b_first = b0;
+    wg.own_first = own_first;
+    wg.nblk = (int)(b_hi - b0 + 1);
+    wg.p_off = (int)(b0 - pb0);
+    wg.warm = (int)std::max(W - b0, 0ll);
+    wg.W = (int)W;
+    wg.M = M;
+    wg.shift = c.load_shift;
+    hipLaunchKernelGGL(null_weights_kernel, dim3((unsigned)((wg.nblk + kNlBlock / 64 - 1) / (kNlBlock / 64))), dim3(kNlBlock), 0, ctx->stream, wg);
+    e = hipGetLastError();
+    if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_null_run_dev: launch failed: %s", hipGetErrorString(e));
+    // ---- the outputs o .. o_end - 1
+    NlApplyArgs ap;
+    for (int p = 0; p < kNlMaxM; p++) ap.in[p] = (const uint8_t*)d_in[p < M ? p : 0] + (o - in_first) * 2;
+    ap.out = (uint8_t*)d_out + (o - out_first) * (out_complex64 ? 8 : 2);
+    ap.Wq = dWq;
+    ap.stats = (unsigned long long*)d_stats;
+    ap.j0 = o;
+    ap.n = o_end - o;
+    ap.blk0 = b0 * Lb;
+    ap.owned = (unsigned long long)((o_end + Lb - 1) / Lb - (o + Lb - 1) / Lb);
+    ap.s = (float)gain * (1.0f / (float)kNlWq);
+    ap.Lb = (int)Lb;
+    ap.M = M;
+    const long long ntiles = (o_end - 1) / kNlTile - o / kNlTile + 1;
+    const unsigned grid = (unsigned)std::min<long long>(ntiles, (long long)kNlMaxGrid);
+    if (out_complex64) hipLaunchKernelGGL(null_apply_kernel<true>, dim3(grid), dim3(kNlBlock), 0, ctx->stream, ap);
+    else hipLaunchKernelGGL(null_apply_kernel<false>, dim3(grid), dim3(kNlBlock), 0, ctx->stream, ap);
+    e = hipGetLastError();
+    if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_null_run_dev: launch failed: %s", hipGetErrorString(e));
+    o = o_end;
+  }
+  return GACQ_OK;
+}

@@ -844,6 +844,69 @@ int gacq_cancel_dev(gacq_ctx* ctx, const gacq_cancel_sat* sats, int K, const gac
                     double* amps_out, unsigned long long* clipped);
 
 /* ---------------------------------------------------------------------------------------------
+ * Spatial nulling with an antenna array (gacq_null.hip): M recordings on one sample clock in, one recording out, under weights that
+ * minimise the output power of every block subject to one linear constraint.  Every decision is a function of the absolute block index,
+ * so the bytes do not depend on how the recording is cut into calls.
+ * Input.  antennas = M in 2..8.  x_p(j), p < M, j >= 0: interleaved int8 I/Q as stored (-128 is a legal value).  d_in is a host array
+ *    of M device pointers, each at any byte address; two antennas may share a pointer.
+ * 1. Block covariance.  block = Lb, a multiple of 64 in 64..32768; block b covers samples b Lb .. (b + 1) Lb - 1.
+ *    C_b[p][q] = sum x_p(j) conj(x_q(j)) over the block, a Gaussian integer.  With the real rows r_2p = I_p, r_2p+1 = Q_p and
+ *    G[u][v] = sum r_u r_v (|G| <= 2^29):  Re C[p][q] = G[2p][2q] + G[2p+1][2q+1],  Im C[p][q] = G[2p+1][2q] - G[2p][2q+1]
+ *    (Im C[p][p] is exactly 0; every component fits int32).
+ * 2. Window.  window = W in 1..64.  R_b = C_(b-W) + .. + C_(b-1) for b >= W; R_b = C_0 + .. + C_(W-1) for b < W (the warm-up).  int64,
+ *    exact, a function of b alone.
+ * 3. Loading.  t = sum_p Re R_b[p][p];  d = (t >> load_shift) + 1, load_shift in 0..40 (10 where a caller has no reason for another);
+ *    A = R_b + d I, every entry converted to fp64 (exact: below 2^53).  d >= 1 keeps A positive definite for all-zero input and for
+ *    antennas that share a buffer.
+ * 4. Weights.  c: M complex doubles (c[2p], c[2p+1] = re, im), all finite, not all zero; (1, 0, .., 0) is power inversion with antenna
+ *    0 as the reference, any other c an MVDR steering vector.  Complex fp64, every real product and every real sum rounded on its own,
+ *    nothing fused; (a + ib)(c + id) = (ac - bd) + i(ad + bc); z / real = (re / real) + i(im / real), two divisions.
+ *      b = c.   for k = 0 .. M-1:  piv_k = Re A[k][k];  for r = k+1 .. M-1:  m = A[r][k] / piv_k;
+ *                                     for q = k+1 .. M-1:  A[r][q] = A[r][q] - m A[k][q];      b[r] = b[r] - m b[k]
+ *      for k = M-1 .. 0:  s = b[k];  for q = k+1 .. M-1 (ascending):  s = s - A[k][q] u[q];      u[k] = s / piv_k
+ *      den = t_0 + t_1 + .. + t_(M-1) (left to right),  t_p = Re c_p Re u_p + Im c_p Im u_p;      w_p = u_p / den
+ *    (Gaussian elimination without pivoting; A - m A[k] is a componentwise subtraction of the product.)  c^H w = 1: with the default c
+ *    the reference antenna passes with gain 1.
+ * 5. Quantised weights.  Per component wq = clamp(rint(w 2^14), -131071, 131071), ties to even, 0 when w 2^14 is not finite; int32 pairs.
+ * 6. Apply.  y(j) = sum_p conj(wq_p(j div Lb)) x_p(j):  re = sum wr xr + wi xi,  im = sum wr xi - wi xr, in int32 (|.| < 2^28, exact in
+ *    any order).
+ * 7. Output.  v = float32(component) (round to nearest even); complex64 v * s with s = float32(gain) * 2^-14 (formed in fp32), one fp32
+ *    multiply per component, nothing fused; or int8 clip(rint(.), -127, 127) of exactly those values, ties to even.
+ * 8. Side outputs, each NULL or device memory.  d_stats: two uint64 that the caller zeroed, 8-byte aligned, added to with vector integer
+ *    atomics: [0] the components of an int8 output that the clip changed (0 for complex64), [1] the owned blocks, those with
+ *    out_first <= b Lb < out_first + n_out; the totals of any partition of the outputs into calls sum to those of one call.
+ *    d_weights: wq of every owned block in block order, int32 [block][M][2].  d_cov: R_b of every owned block, int64 [block][M][M][2].
+ * d_in[p] holds input samples in_first .. in_first + in_count - 1 of antenna p; output samples out_first .. out_first + n_out - 1 are
+ * written to d_out.  Output j in block b needs x_p(j) of every antenna and inputs max(b - W, 0) Lb .. max(b, W) Lb - 1; one that is
+ * needed and not present GACQ_ERR_SHORT_INPUT: a recording shorter than W blocks gives no output, and the last partial block is
+ * produced.  A value outside the ranges above, a c that is not finite or all zero, a gain that is not finite and positive (as a double
+ * and as a float), an index or count below 0 or above 2^48, a complex64 d_out or a d_stats off 8 bytes, a d_weights off 4 or a d_cov
+ * off 8 bytes, a NULL pointer (d_in, one of its entries, d_out) GACQ_ERR_BAD_ARG.  Everything is checked on the host before anything is
+ * launched; a refused call leaves every output untouched; n_out = 0 does nothing.
+ * gacq_null_check makes every check that needs no device pointer, without a context.  gacq_null_open allocates the handle's workspace
+ * (it may wait for the device); gacq_null_run_dev is three launches (block covariances, weights, outputs) per 2^14 blocks on the ctx
+ * stream, asynchronous, without state between calls and without host synchronisation: calls on one handle are ordered by that stream.
+ * The handle is closed before its context is destroyed.  gacq_null_tile: the output samples one workgroup owns (for tests; tiles begin
+ * at absolute sample indices that are multiples of it, a lane's run of 8 samples at multiples of 8), or GACQ_ERR_BAD_ARG.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gacq_null_cfg {
+  int antennas;                    /* M, 2..8 */
+  int block;                       /* Lb: samples per covariance block, a multiple of 64 in 64..32768 */
+  int window;                      /* W: blocks the covariance sums over, 1..64 */
+  int load_shift;                  /* diagonal loading d = (trace >> load_shift) + 1, 0..40 */
+  double c[16];                    /* the constraint: re, im of c_0 .. c_(M-1); the rest is ignored */
+} gacq_null_cfg;
+typedef struct gacq_null gacq_null;
+
+int gacq_null_tile(const gacq_null_cfg* cfg);
+int gacq_null_check(const gacq_null_cfg* cfg, long long in_first, long long in_count, long long out_first, long long n_out, double gain,
+                    int out_complex64);
+int gacq_null_open(gacq_ctx* ctx, const gacq_null_cfg* cfg, gacq_null** out);
+int gacq_null_run_dev(gacq_null* h, const void* const* d_in, long long in_first, long long in_count, long long out_first, long long n_out,
+                      double gain, int out_complex64, void* d_out, void* d_stats, void* d_weights, void* d_cov);
+void gacq_null_close(gacq_null* h);
+
+/* ---------------------------------------------------------------------------------------------
  * Navigation data from tracked prompts (gacq_navbits.hip; the framing is host code, gnss_dsp_tools_amd/navdata.py).
  *
  * gacq_navsym: symbol forming and bit synchronisation of K channels, one workgroup per channel.  Everything is host memory: the call
