@@ -200,20 +200,21 @@ SYMBOLS = {
     "gacq_fold_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_longlong, ctypes.c_void_p,
                                      ctypes.c_void_p]),
-    # synthetic recordings (simulate.py): the gacq_sim_sat array as a plain address
+    # the recording tools: configuration structs, tables and arrays are passed as plain addresses
+    # synthetic recordings (simulate.py): the gacq_sim_sat array
     "gacq_simulate_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_ulonglong,
                                          ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]),
-    # recording ingest (ingest.py): the gacq_ingest_fmt as a plain address
+    # recording ingest (ingest.py): the gacq_ingest_fmt
     "gacq_ingest_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                        ctypes.c_longlong, ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
-    # interference mitigation (mitigate.py): the gacq_mitigate_cfg as a plain address
+    # interference mitigation (mitigate.py): the gacq_mitigate_cfg
     "gacq_mitigate_tile": (ctypes.c_int, [ctypes.c_int]),
     "gacq_mitigate_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                            ctypes.c_longlong, ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
     "gacq_mitigate_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong,
                                          ctypes.c_longlong, ctypes.c_longlong, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_void_p]),
-    # digital down-converter (ddc.py): the gacq_ddc_cfg and the int16 taps as plain addresses
+    # digital down-converter (ddc.py): the gacq_ddc_cfg and the int32 taps
     "gacq_ddc_tile": (ctypes.c_int, [ctypes.c_int]),
     "gacq_ddc_table": (ctypes.c_int, [ctypes.c_void_p]),
     "gacq_ddc_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
@@ -222,7 +223,7 @@ SYMBOLS = {
     "gacq_ddc_run_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                         ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
     "gacq_ddc_close": (None, [ctypes.c_void_p]),
-    # level control and requantiser (requant.py): the gacq_requant_cfg, the float32 gains and the uint64 thresholds as plain addresses
+    # level control and requantiser (requant.py): the gacq_requant_cfg, the float32 gains and the uint64 thresholds
     "gacq_requant_tile": (ctypes.c_int, [ctypes.c_void_p]),
     "gacq_requant_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                           ctypes.c_longlong]),
@@ -230,13 +231,13 @@ SYMBOLS = {
     "gacq_requant_run_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gacq_requant_close": (None, [ctypes.c_void_p]),
-    # cancellation of tracked signals (cancel.py): the gacq_cancel_sat and gacq_cancel_seg arrays as plain addresses
+    # cancellation of tracked signals (cancel.py): the gacq_cancel_sat and gacq_cancel_seg arrays
     "gacq_cancel_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                          ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]),
     "gacq_cancel_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_void_p,
                                        ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    # spatial nulling (nulling.py): the gacq_null_cfg and the host array of device pointers as plain addresses
+    # spatial nulling (nulling.py): the gacq_null_cfg and the host array of device pointers
     "gacq_null_tile": (ctypes.c_int, [ctypes.c_void_p]),
     "gacq_null_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_double,
                                        ctypes.c_int]),

@@ -23,7 +23,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _native as nat
-from . import acquire, chiptrack, codes, handoff as _handoff, longtrack, rawfile, signals, trackloop
+from . import acquire, chiptrack, codes, handoff as _handoff, longtrack, rawfile, signals, streaming, trackloop
 from .mitigate import _count, _device_input
 
 MAX_SATS = 32
@@ -125,19 +125,17 @@ def apply(engine, sats, segs, fs, data, in_first=0, out_first=None, n_out=None, 
     ``out``: a contiguous tensor of that shape and type to write into.
     Returns (output, [complex128 amplitudes per satellite, NaN for a segment that does not touch the output range], clipped components)."""
     torch = nat.require_torch()
-    if dtype not in ("int8", "complex64"):
-        raise ValueError("dtype must be 'int8' or 'complex64', not %r" % (dtype,))
     arr, flat, segs = _sat_structs(sats, segs)
     d, in_c = _device_input(engine, data, in_complex64)
     in_first = int(in_first)
     in_count = _count(d, in_c)
     out_first = in_first if out_first is None else int(out_first)
     n_out = max(0, in_first + in_count - out_first) if n_out is None else int(n_out)
-    cplx = dtype == "complex64"
-    tdtype, numel = (torch.complex64, max(n_out, 0)) if cplx else (torch.int8, 2 * max(n_out, 0))
+    cplx, fresh = streaming.iq_out(n_out if out is None else 0, dtype, d.device)
+    numel = max(n_out, 0) * (1 if cplx else 2)
     if out is None:
-        out = torch.empty(numel, dtype=tdtype, device=d.device)
-    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == tdtype and out.dim() == 1 and out.numel() == numel and out.is_contiguous()):
+        out = fresh
+    elif not (torch.is_tensor(out) and out.is_cuda and out.dtype == fresh.dtype and out.dim() == 1 and out.numel() == numel and out.is_contiguous()):
         raise ValueError("out must be a contiguous 1-D %s CUDA tensor of %d elements" % (dtype, numel))
     amps = np.full(len(flat), np.nan + 1j * np.nan, dtype=np.complex128)
     clipped = ctypes.c_ulonglong(0)
@@ -150,7 +148,7 @@ def apply(engine, sats, segs, fs, data, in_first=0, out_first=None, n_out=None, 
     return out, [amps[cuts[k]:cuts[k + 1]] for k in range(len(segs))], int(clipped.value)
 
 
-class Canceller:
+class Canceller(streaming.Chunks):
     """A recording fed chunk by chunk (bytes or int8 / uint8 / complex64 CUDA tensors): feed(chunk) returns the output samples the chunk
     completes, and the concatenation of what the calls return is what one apply() of the whole recording gives.  With estimate, a
     segment is cancelled once all its samples are there: the input from the first unfinished segment on -- at most one segment per
@@ -162,71 +160,56 @@ class Canceller:
         self.estimate, self.dtype, self.in_complex64 = bool(estimate), dtype, bool(in_complex64)
         _, _, self.segs = _sat_structs(self.sats, segs)
         self.amps = [np.full(len(g), np.nan + 1j * np.nan, dtype=np.complex128) for g in self.segs]
-        self.in_first = int(start)   # absolute index of the first input sample of the kept tail (start: of the first sample fed)
-        self.next_out = int(start)   # the next output sample
         self.clipped = 0
         self.power_in = self.power_out = 0.0
-        self._tail = None
+        super().__init__(64 if self.in_complex64 else 16, lambda in_first, in_count: self._whole(in_first + in_count), self._run, self._whole, start=start)
 
     def _power(self, t):
         torch = nat.require_torch()
         v = torch.view_as_real(t).reshape(-1) if t.dtype.is_complex else t
         return float(v.to(torch.float64).pow(2).sum().item()) if v.numel() else 0.0
 
-    def feed(self, chunk):
-        torch = nat.require_torch()
-        d, _ = _device_input(self.engine, chunk, self.in_complex64)
-        d = (torch.view_as_real(d).reshape(-1) if d.dtype.is_complex else d).view(torch.uint8)
-        if self._tail is not None and self._tail.numel():
-            d = torch.cat([self._tail, d])
-        unit = 8 if self.in_complex64 else 2
-        in_count = d.numel() // unit
-        end = self.in_first + in_count
-        out_end = end
-        if self.estimate:                     # a segment that the input cuts holds the output back to its first sample
+    def _whole(self, end):
+        """`end`, or with estimate the first sample of a segment that `end` cuts: such a segment holds the output back to its first
+        sample, and one that reaches past the outputs is estimated again from there"""
+        back = end
+        if self.estimate:
             for g in self.segs:
                 i = int(np.searchsorted(g["s0"] + g["n"], end, side="right"))
                 if i < len(g) and g["s0"][i] < end:
-                    out_end = min(out_end, int(g["s0"][i]))
-        out_end = max(out_end, self.next_out)
-        n_out = out_end - self.next_out
-        lo = [int(np.searchsorted(g["s0"] + g["n"], self.next_out, side="right")) for g in self.segs]      # the segments that touch the outputs
+                    back = min(back, int(g["s0"][i]))
+        return back
+
+    def _run(self, ds, in_first, in_count, out_first, n_out, k):
+        torch = nat.require_torch()
+        out_end, unit = out_first + n_out, self.sample_bits // 8
+        lo = [int(np.searchsorted(g["s0"] + g["n"], out_first, side="right")) for g in self.segs]      # the segments that touch the outputs
         hi = [max(l, int(np.searchsorted(g["s0"], out_end, side="left"))) for l, g in zip(lo, self.segs)]
-        whole = d[:in_count * unit]
-        x = whole if self.in_complex64 else whole.view(torch.int8)
-        out, amps, clipped = apply(self.engine, self.sats, [g[l:h] for g, l, h in zip(self.segs, lo, hi)], self.fs, x, self.in_first, self.next_out,
-                                   n_out, self.estimate, self.dtype, self.in_complex64)
-        for k, (l, h) in enumerate(zip(lo, hi)):
-            if n_out:
-                self.amps[k][l:h] = amps[k]
+        x = ds[0] if self.in_complex64 else ds[0].view(torch.int8)
+        out, amps, clipped = apply(self.engine, self.sats, [g[l:h] for g, l, h in zip(self.segs, lo, hi)], self.fs, x, in_first, out_first, n_out,
+                                   self.estimate, self.dtype, self.in_complex64)
         self.clipped += clipped
         if n_out:
-            off = (self.next_out - self.in_first) * unit
-            xin = whole[off:off + n_out * unit]
+            for j, (l, h) in enumerate(zip(lo, hi)):
+                self.amps[j][l:h] = amps[j]
+            off = (out_first - in_first) * unit
+            xin = ds[0][off:off + n_out * unit]
             self.power_in += self._power(xin.view(torch.complex64) if self.in_complex64 else xin.view(torch.int8))
             self.power_out += self._power(out)
-        self.next_out = out_end
-        keep = out_end
-        if self.estimate:                     # a whole segment that reaches past the outputs is estimated again from its first sample
-            for g in self.segs:
-                i = int(np.searchsorted(g["s0"] + g["n"], out_end, side="right"))
-                if i < len(g) and g["s0"][i] < out_end:
-                    keep = min(keep, int(g["s0"][i]))
-        keep = max(keep, self.in_first)
-        self._tail = d[(keep - self.in_first) * unit:].clone()
-        self.in_first = keep
         return out
+
+    def feed(self, chunk):
+        torch = nat.require_torch()
+        d, _ = _device_input(self.engine, chunk, self.in_complex64)
+        return self.feed_all([(torch.view_as_real(d).reshape(-1) if d.dtype.is_complex else d).view(torch.uint8)])
 
 
 def cancel_file(engine, sats, segs, fs, fin, fout, estimate=True, dtype="int8", in_complex64=False, piece_bytes=rawfile.PIECE_BYTES):
     """Cancel the open binary file fin into fout piece by piece.  (samples written, Canceller with the totals)."""
-    unit = 8 if in_complex64 else 2
-    can, n = Canceller(engine, sats, segs, fs, estimate, dtype, in_complex64), 0
-    for piece in rawfile.read_pieces(fin, unit, piece_bytes):
-        out = can.feed(piece.view(np.uint8))
-        n += out.numel() // (2 if dtype == "int8" else 1)
-        fout.write(out.cpu().numpy().tobytes())
-    return n, can
+    can = Canceller(engine, sats, segs, fs, estimate, dtype, in_complex64)
+    n = streaming.pump(rawfile.read_pieces(fin, 8 if in_complex64 else 2, piece_bytes), lambda held: lambda piece: [can.feed(piece.view(np.uint8))], [fout],
+                       2 if dtype == "int8" else 1)
+    return n[0] if n else 0, can
 
 
 def _cancel_tracked(name, iq_int8, fs, coffset, items=None, min_metric=None, skip=0, **handoff_kw):
@@ -342,12 +325,7 @@ def run(name, argv, out=None):
 
 
 def main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
-    if not argv or argv[0] in ("-h", "--help"):
-        print(__doc__)
-        return 0
-    run(argv[0], argv[1:])
-    return 0
+    return streaming.main(argv, __doc__, lambda argv: run(argv[0], argv[1:]))
 
 
 if __name__ == "__main__":

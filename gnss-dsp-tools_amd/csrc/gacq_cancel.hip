@@ -38,7 +38,6 @@ constexpr int kCanMaxK = 32;
 constexpr int kCanMaxSegs = 1 << 20;
 constexpr long long kCanMaxN = 1ll << 24;
 constexpr int kCanMaxChips = 10240;             // the tracking loops' limit
-constexpr long long kCanMaxIndex = 1ll << 48;
 constexpr unsigned kCanMaxGrid = 1u << 16;      // workgroups; a longer call loops
 constexpr unsigned long long kCanTmbocMask = (1ull << 0) | (1ull << 4) | (1ull << 6) | (1ull << 29);
 
@@ -325,6 +324,12 @@ __global__ __launch_bounds__(kCanBlock) void cancel_subtract_kernel(const CanArg
   }
 }
 
+}  // namespace
+
+#include "gacq_streamhost.h"
+
+namespace {
+
 // floor(frac(v) 2^64) mod 2^64, in IEEE double operations (as gacq_simulate.hip and tests/simulate_oracle.py have it)
 unsigned long long can_turns(double v) {
   const double t = v - std::floor(v);                               // [0, 1]; 1 only when a tiny negative v rounds up
@@ -346,10 +351,7 @@ int can_check(const gacq_cancel_sat* sats, int K, const gacq_cancel_seg* segs, d
   if (!sats || !segs || !d_in || !d_out) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: NULL argument");
   if (K < 1 || K > kCanMaxK) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: need 1 <= K <= %d satellites (K %d)", kCanMaxK, K);
   if (!std::isfinite(fs) || !(fs > 0.0)) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: fs must be finite and positive");
-  if (in_first < 0 || in_count < 0 || out_first < 0 || n_out < 0 || in_first > kCanMaxIndex || in_count > kCanMaxIndex || out_first > kCanMaxIndex ||
-      n_out > kCanMaxIndex)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: need 0 <= in_first, in_count, out_first, n_out <= 2^48 (%lld, %lld, %lld, %lld)", in_first,
-                     in_count, out_first, n_out);
+  if (const int rc = st_check_range(nullptr, "gacq_cancel", in_first, in_count, out_first, n_out)) return rc;
   if (in_complex64 && (uintptr_t)d_in % 8u) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: complex64 input must be 8-byte aligned");
   if (out_complex64 && (uintptr_t)d_out % 8u) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: complex64 output must be 8-byte aligned");
   long long total = 0;
@@ -375,7 +377,7 @@ int can_check(const gacq_cancel_sat* sats, int K, const gacq_cancel_seg* segs, d
       if (!std::isfinite(g->carrier_hz) || !std::isfinite(g->carrier_phase) || !std::isfinite(g->code_rate_hz) || !std::isfinite(g->code_phase) ||
           !std::isfinite(g->amp_re) || !std::isfinite(g->amp_im))
         return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: satellite %d, segment %d: a parameter is not finite", k, i);
-      if (g->n < 1 || g->n > kCanMaxN || g->s0 < 0 || g->s0 > kCanMaxIndex - g->n)
+      if (g->n < 1 || g->n > kCanMaxN || g->s0 < 0 || g->s0 > kStreamMaxIndex - g->n)
         return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: satellite %d, segment %d: need 1 <= n <= 2^24, s0 >= 0 and s0 + n <= 2^48 (s0 %lld, n %lld)",
                          k, i, g->s0, g->n);
       if (!(g->code_rate_hz > 0.0) || !(g->code_rate_hz / fs < 16.0))
@@ -414,7 +416,7 @@ extern "C" int gacq_cancel_dev(gacq_ctx* ctx, const gacq_cancel_sat* sats, int K
   // everything is checked before anything is allocated or launched
   int Ls[kCanMaxK];
   int rc = can_check(sats, K, segs, fs, estimate, d_in, in_complex64, in_first, in_count, out_first, n_out, out_complex64, d_out, Ls);
-  if (rc < 0) return set_error(ctx, rc, "%s", gacq_last_error(nullptr));
+  if (rc < 0) return st_forward(ctx, rc);
   if (n_out == 0) return GACQ_OK;
   std::vector<ChipTable> tabs(K);
   for (int k = 0; k < K; k++)

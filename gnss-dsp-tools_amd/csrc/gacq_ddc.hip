@@ -52,7 +52,6 @@ constexpr int kDdcZWords = 9216;                 // >= D pitch for every (D, T):
 constexpr int kDdcTapWords = 768;                // >= D nt4 for every (D, T): at D = 61..64
 constexpr int kDdcLeadWords = kDdcMaxDecim + kDdcTapWords;      // per lead: the rows' step counts, then the rows' taps
 constexpr unsigned kDdcMaxGrid = 1u << 16;       // workgroups; a longer call loops
-constexpr long long kDdcMaxIndex = 1ll << 48;
 constexpr bool kTableInLds = GACQ_DDC_TABLE_LDS != 0;
 
 struct DdcLayout {
@@ -263,12 +262,14 @@ void ddc_table(int16_t* w) {
 
 }  // namespace
 
+#include "gacq_streamhost.h"
+
 struct gacq_ddc {
   gacq_ctx* ctx = nullptr;
   gacq_ddc_cfg cfg{};
   std::vector<int32_t> taps;
   DdcLayout lay{};
-  void* dev = nullptr;          // the table, then kDdcLeads tap layouts
+  StDevBlock dev;               // the table, then kDdcLeads tap layouts
 };
 
 extern "C" int gacq_ddc_tile(int D) {
@@ -292,20 +293,11 @@ extern "C" int gacq_ddc_check(const gacq_ddc_cfg* cfg, const int32_t* taps, int 
   long long sum = 0;
   for (int k = 0; k < T; k++) sum += std::llabs((long long)taps[k]);
   if (sum > 65536) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_ddc: the taps' magnitudes sum to %lld, above 65536", sum);
-  const float g = (float)gain;
-  if (!std::isfinite(gain) || !(gain > 0.0) || !std::isfinite(g) || !(g > 0.0f))
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_ddc: the gain must be finite and positive in fp32 (%g)", gain);
-  if (in_first < 0 || in_count < 0 || out_first < 0 || n_out < 0 || in_first > kDdcMaxIndex || in_count > kDdcMaxIndex || out_first > kDdcMaxIndex ||
-      n_out > kDdcMaxIndex)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_ddc: need 0 <= in_first, in_count, out_first, n_out <= 2^48 (%lld, %lld, %lld, %lld)", in_first,
-                     in_count, out_first, n_out);
-  if (n_out == 0) return GACQ_OK;
-  const long long H = T / 2, D = cfg->decim, last = out_first + n_out - 1;
-  const long long need_lo = std::max(0ll, out_first * D - H), need_hi = last * D + H;
-  if (need_lo < in_first || need_hi >= in_first + in_count)
-    return set_error(nullptr, GACQ_ERR_SHORT_INPUT, "gacq_ddc: outputs %lld .. %lld need input samples %lld .. %lld, present are %lld .. %lld", out_first,
-                     last, need_lo, need_hi, in_first, in_first + in_count - 1);
-  return GACQ_OK;
+  int rc = st_check_gain(nullptr, "gacq_ddc", "must be finite and positive in fp32", gain);
+  if (rc == GACQ_OK) rc = st_check_range(nullptr, "gacq_ddc", in_first, in_count, out_first, n_out);
+  if (rc < 0 || n_out == 0) return rc;
+  const long long H = T / 2, D = cfg->decim;
+  return st_check_support(nullptr, "gacq_ddc", out_first, n_out, std::max(0ll, out_first * D - H), (out_first + n_out - 1) * D + H, in_first, in_count);
 }
 
 extern "C" int gacq_ddc_open(gacq_ctx* ctx, const gacq_ddc_cfg* cfg, const int32_t* taps, int T, gacq_ddc** out) {
@@ -313,7 +305,7 @@ extern "C" int gacq_ddc_open(gacq_ctx* ctx, const gacq_ddc_cfg* cfg, const int32
   if (!out) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_ddc_open: NULL argument");
   *out = nullptr;
   const int rc = gacq_ddc_check(cfg, taps, T, 0, 0, 0, 0, 1.0, 0);
-  if (rc < 0) return set_error(ctx, rc, "%s", gacq_last_error(nullptr));
+  if (rc < 0) return st_forward(ctx, rc);
   const int D = cfg->decim, H = T / 2;
   const DdcLayout lay = layout_of(D, T);
   if (D * lay.pitch > kDdcZWords || D * lay.nt4 > kDdcTapWords || 2 * kDdcBlock * 4 > kDdcZWords)
@@ -336,34 +328,22 @@ extern "C" int gacq_ddc_open(gacq_ctx* ctx, const gacq_ddc_cfg* cfg, const int32
       steps[r] = (last + 4) / 4;
     }
   }
-  gacq_ddc* h = new gacq_ddc;
+  std::unique_ptr<gacq_ddc> h(new gacq_ddc);
   h->ctx = ctx;
   h->cfg = *cfg;
   h->taps.assign(taps, taps + T);
   h->lay = lay;
   {
     GACQ_DEVICE(ctx);
-    hipError_t e = hipMalloc(&h->dev, host.size() * sizeof(int));
-    // the upload is a blocking copy from pageable memory: it has landed when the call returns
-    if (e == hipSuccess) e = hipMemcpy(h->dev, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      if (h->dev) (void)hipFree(h->dev);
-      delete h;
-      return set_error(ctx, GACQ_ERR_HIP, "gacq_ddc_open: %s", hipGetErrorString(e));
-    }
+    hipError_t e = h->dev.alloc(ctx, host.size() * sizeof(int));
+    if (e == hipSuccess) e = h->dev.upload(0, host.data(), host.size() * sizeof(int));
+    if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_ddc_open: %s", hipGetErrorString(e));
   }
-  *out = h;
+  *out = h.release();
   return GACQ_OK;
 }
 
-extern "C" void gacq_ddc_close(gacq_ddc* h) {
-  if (!h) return;
-  if (h->dev) {
-    DeviceGuard guard(h->ctx->device);
-    (void)hipFree(h->dev);
-  }
-  delete h;
-}
+extern "C" void gacq_ddc_close(gacq_ddc* h) { delete h; }
 
 extern "C" int gacq_ddc_run_dev(gacq_ddc* h, const void* d_in, long long in_first, long long in_count, long long out_first, long long n_out,
                                 double gain, int out_complex64, void* d_out) {
@@ -373,7 +353,7 @@ extern "C" int gacq_ddc_run_dev(gacq_ddc* h, const void* d_in, long long in_firs
   // everything is checked before anything is launched
   const int T = (int)h->taps.size(), H = T / 2, D = h->cfg.decim;
   const int rc = gacq_ddc_check(&h->cfg, h->taps.data(), T, in_first, in_count, out_first, n_out, gain, out_complex64);
-  if (rc < 0) return set_error(ctx, rc, "%s", gacq_last_error(nullptr));
+  if (rc < 0) return st_forward(ctx, rc);
   if (out_complex64 && (uintptr_t)d_out % 8u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_ddc_run_dev: complex64 output must be 8-byte aligned");
   if (n_out == 0) return GACQ_OK;
   // slot 0 of a tile's image: `lead` samples below the first one the tile needs, on a 16-byte boundary of an even d_in (a tile's
@@ -384,8 +364,8 @@ extern "C" int gacq_ddc_run_dev(gacq_ddc* h, const void* d_in, long long in_firs
   DdcArgs a;
   a.in = (const uint8_t*)d_in;
   a.out = d_out;
-  a.tab = (const unsigned*)h->dev;
-  a.taps = (const int*)h->dev + kDdcTable + lead * kDdcLeadWords;
+  a.tab = (const unsigned*)h->dev.p;
+  a.taps = (const int*)h->dev.p + kDdcTable + lead * kDdcLeadWords;
   a.nbase = first_needed - lead;
   a.in_first = in_first;
   a.in_count = in_count;
@@ -406,7 +386,5 @@ extern "C" int gacq_ddc_run_dev(gacq_ddc* h, const void* d_in, long long in_firs
   const unsigned grid = (unsigned)std::min<long long>(ntiles, (long long)kDdcMaxGrid);
   if (out_complex64) hipLaunchKernelGGL((ddc_kernel<true>), dim3(grid), dim3(kDdcBlock), 0, ctx->stream, a);
   else hipLaunchKernelGGL((ddc_kernel<false>), dim3(grid), dim3(kDdcBlock), 0, ctx->stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_ddc_run_dev: launch failed: %s", hipGetErrorString(e));
-  return GACQ_OK;
+  return st_launched(ctx, "gacq_ddc_run_dev");
 }

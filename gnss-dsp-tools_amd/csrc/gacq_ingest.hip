@@ -41,7 +41,6 @@ constexpr int kTile = kIngBlock * kRun;          // real mode: outputs per workg
 constexpr int kLead = 32;                        // real mode: LDS slot 0 holds input 2 M0 - kLead (>= 21, a multiple of 16)
 constexpr int kLdsVals = 2 * kTile + 64;         // 4160 >= kLead + 2 (kTile - 1) + 21 + 1, a multiple of 16; the last lane reads up to 4159
 constexpr unsigned kIngMaxGrid = 1u << 16;       // workgroups; a longer call loops
-constexpr long long kIngMaxIndex = 1ll << 48;
 
 constexpr int kCentre = 16384;                   // g[0]
 // g[k] s(k), k = 1, 3, .., 21: the odd taps of the Hann-windowed sinc (include/gacq.h has g) times the sign of i^k
@@ -326,6 +325,8 @@ void launch(bool real, bool cplx, unsigned grid, hipStream_t stream, const IngAr
 
 }  // namespace
 
+#include "gacq_streamhost.h"
+
 extern "C" int gacq_ingest_dev(gacq_ctx* ctx, const gacq_ingest_fmt* fmt, const void* d_in, long long in_first, long long in_count,
                                long long out_first, long long n_out, double gain, int out_complex64, void* d_out) {
   if (!ctx) return GACQ_ERR_BAD_ARG;
@@ -339,12 +340,9 @@ extern "C" int gacq_ingest_dev(gacq_ctx* ctx, const gacq_ingest_fmt* fmt, const 
   if (real && (fmt->container == GACQ_INGEST_S16 || fmt->container == GACQ_INGEST_F32))
     return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_ingest_dev: real mode takes s8, u8 and packed input only");
   const float g = (float)gain;
-  if (!std::isfinite(gain) || !(gain > 0.0) || !std::isfinite(g) || !(g > 0.0f))
-    return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_ingest_dev: the gain must be finite and positive in fp32 (%g)", gain);
-  if (in_first < 0 || in_count < 0 || out_first < 0 || n_out < 0 || in_first > kIngMaxIndex || in_count > kIngMaxIndex || out_first > kIngMaxIndex ||
-      n_out > kIngMaxIndex)
-    return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_ingest_dev: need 0 <= in_first, in_count, out_first, n_out <= 2^48 (%lld, %lld, %lld, %lld)", in_first,
-                     in_count, out_first, n_out);
+  int rc = st_check_gain(ctx, "gacq_ingest_dev", "must be finite and positive in fp32", gain);
+  if (rc == GACQ_OK) rc = st_check_range(ctx, "gacq_ingest_dev", in_first, in_count, out_first, n_out);
+  if (rc < 0) return rc;
   const int vbits = packed ? fmt->bits : fmt->container == GACQ_INGEST_S16 ? 16 : fmt->container == GACQ_INGEST_F32 ? 32 : 8;
   const int vps = real ? 1 : 2;                                       // values per input sample
   if ((in_first * vps * vbits) % 8)
@@ -354,9 +352,7 @@ extern "C" int gacq_ingest_dev(gacq_ctx* ctx, const gacq_ingest_fmt* fmt, const 
   // what the outputs need: I/Q sample m; real inputs 2m - 21 .. 2m + 21, those below 0 being zero
   const long long last = out_first + n_out - 1;
   const long long need_lo = real ? std::max(0ll, 2 * out_first - 21) : out_first, need_hi = real ? 2 * last + 21 : last;
-  if (need_lo < in_first || need_hi >= in_first + in_count)
-    return set_error(ctx, GACQ_ERR_SHORT_INPUT, "gacq_ingest_dev: outputs %lld .. %lld need input samples %lld .. %lld, present are %lld .. %lld", out_first,
-                     last, need_lo, need_hi, in_first, in_first + in_count - 1);
+  if ((rc = st_check_support(ctx, "gacq_ingest_dev", out_first, n_out, need_lo, need_hi, in_first, in_count)) < 0) return rc;
   IngArgs a;
   a.in = (const uint8_t*)d_in;
   a.out = d_out;
@@ -405,7 +401,5 @@ extern "C" int gacq_ingest_dev(gacq_ctx* ctx, const gacq_ingest_fmt* fmt, const 
       else if (fmt->bits == 2) launch<kP2>(real, cplx, grid, ctx->stream, a);
       else launch<kP4>(real, cplx, grid, ctx->stream, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_ingest_dev: launch failed: %s", hipGetErrorString(e));
-  return GACQ_OK;
+  return st_launched(ctx, "gacq_ingest_dev");
 }

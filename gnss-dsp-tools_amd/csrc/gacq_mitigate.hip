@@ -43,7 +43,6 @@ constexpr int kRun = 8;                          // blank-only kernel: outputs p
 constexpr int kBlkTile = kBlkThreads * kRun;
 constexpr int kBlkGroups = (kBlkTile + 2 * kHalo) / 8;      // hit bytes of a tile and its halos
 constexpr unsigned kMitMaxGrid = 1u << 16;       // workgroups; a longer call loops
-constexpr long long kMitMaxIndex = 1ll << 48;
 
 constexpr int mit_threads(int log2n) { return (1 << log2n) / 8 < 64 ? 64 : ((1 << log2n) / 8 > 512 ? 512 : (1 << log2n) / 8); }
 
@@ -587,6 +586,8 @@ int ilog2(int n) {
 
 }  // namespace
 
+#include "gacq_streamhost.h"
+
 extern "C" int gacq_mitigate_tile(int nfft) {
   if (nfft < 64 || nfft > 4096 || (nfft & (nfft - 1))) return GACQ_ERR_BAD_ARG;
   return kMitTile;
@@ -608,13 +609,9 @@ extern "C" int gacq_mitigate_check(const gacq_mitigate_cfg* cfg, const void* d_i
     if (!std::isfinite(cfg->ratio) || !(cfg->ratio > 1.0))
       return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_mitigate_dev: the ratio must be finite and above 1 (%g)", cfg->ratio);
   }
-  const float g = (float)gain;
-  if (!std::isfinite(gain) || !(gain > 0.0) || !std::isfinite(g) || !(g > 0.0f))
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_mitigate_dev: the gain must be finite and positive in fp32 (%g)", gain);
-  if (in_first < 0 || in_count < 0 || out_first < 0 || n_out < 0 || in_first > kMitMaxIndex || in_count > kMitMaxIndex || out_first > kMitMaxIndex ||
-      n_out > kMitMaxIndex)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_mitigate_dev: need 0 <= in_first, in_count, out_first, n_out <= 2^48 (%lld, %lld, %lld, %lld)",
-                     in_first, in_count, out_first, n_out);
+  int rc = st_check_gain(nullptr, "gacq_mitigate_dev", "must be finite and positive in fp32", gain);
+  if (rc == GACQ_OK) rc = st_check_range(nullptr, "gacq_mitigate_dev", in_first, in_count, out_first, n_out);
+  if (rc < 0) return rc;
   if ((in_complex64 && (uintptr_t)d_in % 8u) || (out_complex64 && (uintptr_t)d_out % 8u))
     return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_mitigate_dev: a complex64 buffer must be 8-byte aligned");
   if (n_out == 0) return GACQ_OK;
@@ -628,11 +625,7 @@ extern "C" int gacq_mitigate_check(const gacq_mitigate_cfg* cfg, const void* d_i
     need_lo = out_first - cfg->hold;
     need_hi = last + cfg->hold;
   }
-  need_lo = std::max(0ll, need_lo);
-  if (need_lo < in_first || need_hi >= in_first + in_count)
-    return set_error(nullptr, GACQ_ERR_SHORT_INPUT, "gacq_mitigate_dev: outputs %lld .. %lld need input samples %lld .. %lld, present are %lld .. %lld",
-                     out_first, last, need_lo, need_hi, in_first, in_first + in_count - 1);
-  return GACQ_OK;
+  return st_check_support(nullptr, "gacq_mitigate_dev", out_first, n_out, std::max(0ll, need_lo), need_hi, in_first, in_count);
 }
 
 extern "C" int gacq_mitigate_dev(gacq_ctx* ctx, const gacq_mitigate_cfg* cfg, const void* d_in, int in_complex64, long long in_first,
@@ -640,10 +633,7 @@ extern "C" int gacq_mitigate_dev(gacq_ctx* ctx, const gacq_mitigate_cfg* cfg, co
                                  void* d_stats, void* d_frame_bins) {
   // everything is checked before anything is launched
   const int rc = gacq_mitigate_check(cfg, d_in, in_complex64, in_first, in_count, out_first, n_out, gain, out_complex64, d_out);
-  if (rc < 0) {
-    if (ctx) set_error(ctx, rc, "%s", gacq_last_error(nullptr));
-    return rc;
-  }
+  if (rc < 0) return ctx ? st_forward(ctx, rc) : rc;
   if (!ctx) return GACQ_ERR_BAD_ARG;
   if (((uintptr_t)d_stats % 8u) || ((uintptr_t)d_frame_bins % 4u))
     return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_mitigate_dev: d_stats must be 8-byte and d_frame_bins 4-byte aligned");
@@ -712,7 +702,5 @@ extern "C" int gacq_mitigate_dev(gacq_ctx* ctx, const gacq_mitigate_cfg* cfg, co
       default: launch_excise<12>(grid, ctx->stream, a);
     }
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_mitigate_dev: launch failed: %s", hipGetErrorString(e));
-  return GACQ_OK;
+  return st_launched(ctx, "gacq_mitigate_dev");
 }

@@ -34,7 +34,6 @@ namespace {
 
 constexpr int kNlBlock = 256;
 constexpr int kNlMaxM = 8, kNlMaxWindow = 64, kNlMaxLb = 32768, kNlMaxShift = 40;
-constexpr long long kNlMaxIndex = 1ll << 48;
 constexpr long long kNlChunkBlocks = 1ll << 14;      // blocks whose outputs one triple of launches writes, at most (2^29 samples)
 constexpr int kNlRuns = 8;                           // runs a lane works through
 constexpr int kNlTile = kNlBlock * kNlRuns * 8;      // 16384 samples a workgroup
@@ -341,10 +340,12 @@ int check_cfg(const gacq_null_cfg* c) {
 
 }  // namespace
 
+#include "gacq_streamhost.h"
+
 struct gacq_null {
   gacq_ctx* ctx = nullptr;
   gacq_null_cfg cfg{};
-  void* dev = nullptr;          // the block covariances of a triple of launches, then the weights of its blocks
+  StDevBlock dev;               // the block covariances of a triple of launches, then the weights of its blocks
 };
 
 extern "C" int gacq_null_tile(const gacq_null_cfg* cfg) {
@@ -354,22 +355,12 @@ extern "C" int gacq_null_tile(const gacq_null_cfg* cfg) {
 
 extern "C" int gacq_null_check(const gacq_null_cfg* cfg, long long in_first, long long in_count, long long out_first, long long n_out, double gain,
                                int out_complex64) {
-  const int rc = check_cfg(cfg);
-  if (rc < 0) return rc;
   (void)out_complex64;                                                  // either form takes every range
-  if (!std::isfinite(gain) || !(gain > 0.0) || !std::isfinite((float)gain) || !((float)gain > 0.0f))
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: the gain is not finite and positive (%g)", gain);
-  if (in_first < 0 || in_count < 0 || out_first < 0 || n_out < 0 || in_first > kNlMaxIndex || in_count > kNlMaxIndex || out_first > kNlMaxIndex ||
-      n_out > kNlMaxIndex)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: need 0 <= in_first, in_count, out_first, n_out <= 2^48 (%lld, %lld, %lld, %lld)", in_first,
-                     in_count, out_first, n_out);
-  if (n_out == 0) return GACQ_OK;
-  const long long Lb = cfg->block, W = cfg->window, b_lo = out_first / Lb;
-  const long long need_lo = std::max(b_lo - W, 0ll) * Lb, need_hi = std::max(out_first + n_out, W * Lb) - 1;
-  if (need_lo < in_first || need_hi >= in_first + in_count)
-    return set_error(nullptr, GACQ_ERR_SHORT_INPUT, "gacq_null: outputs %lld .. %lld need input samples %lld .. %lld, present are %lld .. %lld", out_first,
-                     out_first + n_out - 1, need_lo, need_hi, in_first, in_first + in_count - 1);
-  return GACQ_OK;
+  int rc = check_cfg(cfg);
+  if (rc == GACQ_OK) rc = st_check_gain(nullptr, "gacq_null", "is not finite and positive", gain);
+  if (rc == GACQ_OK) rc = st_check_range(nullptr, "gacq_null", in_first, in_count, out_first, n_out);
+  if (rc < 0 || n_out == 0) return rc;
+  return st_check_block_support(nullptr, "gacq_null", cfg->block, cfg->window, out_first, n_out, in_first, in_count);
 }
 
 extern "C" int gacq_null_open(gacq_ctx* ctx, const gacq_null_cfg* cfg, gacq_null** out) {
@@ -377,30 +368,20 @@ extern "C" int gacq_null_open(gacq_ctx* ctx, const gacq_null_cfg* cfg, gacq_null
   if (!out) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_open: NULL argument");
   *out = nullptr;
   const int rc = gacq_null_check(cfg, 0, 0, 0, 0, 1.0, 0);
-  if (rc < 0) return set_error(ctx, rc, "%s", gacq_last_error(nullptr));
-  gacq_null* h = new gacq_null;
+  if (rc < 0) return st_forward(ctx, rc);
+  std::unique_ptr<gacq_null> h(new gacq_null);
   h->ctx = ctx;
   h->cfg = *cfg;
   {
     GACQ_DEVICE(ctx);
-    const hipError_t e = hipMalloc(&h->dev, ((size_t)(kNlChunkBlocks + kNlMaxWindow) * 128 + (size_t)kNlChunkBlocks * 16) * sizeof(int));
-    if (e != hipSuccess) {
-      delete h;
-      return set_error(ctx, GACQ_ERR_HIP, "gacq_null_open: %s", hipGetErrorString(e));
-    }
+    const hipError_t e = h->dev.alloc(ctx, ((size_t)(kNlChunkBlocks + kNlMaxWindow) * 128 + (size_t)kNlChunkBlocks * 16) * sizeof(int));
+    if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_null_open: %s", hipGetErrorString(e));
   }
-  *out = h;
+  *out = h.release();
   return GACQ_OK;
 }
 
-extern "C" void gacq_null_close(gacq_null* h) {
-  if (!h) return;
-  if (h->dev) {
-    DeviceGuard guard(h->ctx->device);
-    (void)hipFree(h->dev);
-  }
-  delete h;
-}
+extern "C" void gacq_null_close(gacq_null* h) { delete h; }
 
 extern "C" int gacq_null_run_dev(gacq_null* h, const void* const* d_in, long long in_first, long long in_count, long long out_first, long long n_out,
                                  double gain, int out_complex64, void* d_out, void* d_stats, void* d_weights, void* d_cov) {
@@ -411,8 +392,8 @@ extern "C" int gacq_null_run_dev(gacq_null* h, const void* const* d_in, long lon
   for (int p = 0; p < c.antennas; p++)
     if (!d_in[p]) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: the pointer of antenna %d is NULL", p);
   // everything is checked before anything is launched
-  const int rc = gacq_null_check(&c, in_first, in_count, out_first, n_out, gain, out_complex64);
-  if (rc < 0) return set_error(ctx, rc, "%s", gacq_last_error(nullptr));
+  int rc = gacq_null_check(&c, in_first, in_count, out_first, n_out, gain, out_complex64);
+  if (rc < 0) return st_forward(ctx, rc);
   if (out_complex64 && (uintptr_t)d_out % 8u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: complex64 output must be 8-byte aligned");
   if ((uintptr_t)d_stats % 8u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: d_stats must be 8-byte aligned");
   if ((uintptr_t)d_weights % 4u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: d_weights must be 4-byte aligned");
@@ -421,7 +402,7 @@ extern "C" int gacq_null_run_dev(gacq_null* h, const void* const* d_in, long lon
   const int M = c.antennas;
   const long long Lb = c.block, W = c.window, out_end = out_first + n_out;
   const long long own_first = (out_first + Lb - 1) / Lb;
-  int* dC = (int*)h->dev;
+  int* dC = (int*)h->dev.p;
   int* dWq = dC + (size_t)(kNlChunkBlocks + kNlMaxWindow) * 128;
   GACQ_DEVICE(ctx);
   for (long long o = out_first; o < out_end;) {
@@ -437,8 +418,7 @@ extern "C" int gacq_null_run_dev(gacq_null* h, const void* const* d_in, long lon
     cv.wpb_log2 = Lb >= 256 ? 2 : Lb >= 128 ? 1 : 0;
     const long long per = (kNlBlock / 64) >> cv.wpb_log2, npass = (cv.nblk + per - 1) / per;
     hipLaunchKernelGGL(null_cov_kernel, dim3((unsigned)std::min<long long>(npass, (long long)kNlMaxGrid)), dim3(kNlBlock), 0, ctx->stream, cv);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_null_run_dev: launch failed: %s", hipGetErrorString(e));
+    if ((rc = st_launched(ctx, "gacq_null_run_dev")) < 0) return rc;
     // ---- the weights of blocks b0 .. b_hi
     NlWgtArgs wg;
     wg.C = dC;
@@ -455,8 +435,7 @@ extern "C" int gacq_null_run_dev(gacq_null* h, const void* const* d_in, long lon
     wg.M = M;
     wg.shift = c.load_shift;
     hipLaunchKernelGGL(null_weights_kernel, dim3((unsigned)((wg.nblk + kNlBlock / 64 - 1) / (kNlBlock / 64))), dim3(kNlBlock), 0, ctx->stream, wg);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_null_run_dev: launch failed: %s", hipGetErrorString(e));
+    if ((rc = st_launched(ctx, "gacq_null_run_dev")) < 0) return rc;
     // ---- the outputs o .. o_end - 1
     NlApplyArgs ap;
     for (int p = 0; p < kNlMaxM; p++) ap.in[p] = (const uint8_t*)d_in[p < M ? p : 0] + (o - in_first) * 2;
@@ -474,8 +453,7 @@ extern "C" int gacq_null_run_dev(gacq_null* h, const void* const* d_in, long lon
     const unsigned grid = (unsigned)std::min<long long>(ntiles, (long long)kNlMaxGrid);
     if (out_complex64) hipLaunchKernelGGL(null_apply_kernel<true>, dim3(grid), dim3(kNlBlock), 0, ctx->stream, ap);
     else hipLaunchKernelGGL(null_apply_kernel<false>, dim3(grid), dim3(kNlBlock), 0, ctx->stream, ap);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_null_run_dev: launch failed: %s", hipGetErrorString(e));
+    if ((rc = st_launched(ctx, "gacq_null_run_dev")) < 0) return rc;
     o = o_end;
   }
   return GACQ_OK;

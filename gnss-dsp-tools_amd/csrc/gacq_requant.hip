@@ -37,7 +37,6 @@ namespace {
 
 constexpr int kRqBlock = 256;
 constexpr int kRqMaxGains = 256, kRqMaxWindow = 64, kRqMaxLb = 65536;
-constexpr long long kRqMaxIndex = 1ll << 48;
 constexpr long long kRqChunkBlocks = 1ll << 16;      // blocks whose outputs one pair of launches writes, at most
 constexpr long long kRqChunkComps = 1ll << 28;       // ... and components: the quantize kernel counts them, and the output's bytes, in 32 bits
 constexpr unsigned kRqMaxGrid = 1u << 16;            // workgroups; a longer call loops
@@ -355,12 +354,14 @@ int check_cfg(const gacq_requant_cfg* c, const float* gains, const uint64_t* thr
 
 }  // namespace
 
+#include "gacq_streamhost.h"
+
 struct gacq_requant {
   gacq_ctx* ctx = nullptr;
   gacq_requant_cfg cfg{};
   std::vector<float> gains;
   std::vector<uint64_t> thresholds;
-  void* dev = nullptr;          // 256 thresholds, the block powers of a pair of launches, 256 gains
+  StDevBlock dev;               // 256 thresholds, the block powers of a pair of launches, 256 gains
 };
 
 extern "C" int gacq_requant_tile(const gacq_requant_cfg* cfg) {
@@ -375,12 +376,9 @@ extern "C" int gacq_requant_tile(const gacq_requant_cfg* cfg) {
 
 extern "C" int gacq_requant_check(const gacq_requant_cfg* cfg, const float* gains, const uint64_t* thresholds, long long in_first, long long in_count,
                                   long long out_first, long long n_out) {
-  const int rc = check_cfg(cfg, gains, thresholds);
+  int rc = check_cfg(cfg, gains, thresholds);
+  if (rc == GACQ_OK) rc = st_check_range(nullptr, "gacq_requant", in_first, in_count, out_first, n_out);
   if (rc < 0) return rc;
-  if (in_first < 0 || in_count < 0 || out_first < 0 || n_out < 0 || in_first > kRqMaxIndex || in_count > kRqMaxIndex || out_first > kRqMaxIndex ||
-      n_out > kRqMaxIndex)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_requant: need 0 <= in_first, in_count, out_first, n_out <= 2^48 (%lld, %lld, %lld, %lld)", in_first,
-                     in_count, out_first, n_out);
   if (cfg->container == GACQ_INGEST_PACKED) {
     const int unit = 4 / cfg->bits;
     if (out_first % unit || n_out % unit)
@@ -388,12 +386,7 @@ extern "C" int gacq_requant_check(const gacq_requant_cfg* cfg, const float* gain
                        out_first, n_out);
   }
   if (n_out == 0) return GACQ_OK;
-  const long long Lb = cfg->block, W = cfg->window, b_lo = out_first / Lb;
-  const long long need_lo = std::max(b_lo - W, 0ll) * Lb, need_hi = std::max(out_first + n_out, W * Lb) - 1;
-  if (need_lo < in_first || need_hi >= in_first + in_count)
-    return set_error(nullptr, GACQ_ERR_SHORT_INPUT, "gacq_requant: outputs %lld .. %lld need input samples %lld .. %lld, present are %lld .. %lld", out_first,
-                     out_first + n_out - 1, need_lo, need_hi, in_first, in_first + in_count - 1);
-  return GACQ_OK;
+  return st_check_block_support(nullptr, "gacq_requant", cfg->block, cfg->window, out_first, n_out, in_first, in_count);
 }
 
 extern "C" int gacq_requant_open(gacq_ctx* ctx, const gacq_requant_cfg* cfg, const float* gains, const uint64_t* thresholds, gacq_requant** out) {
@@ -401,8 +394,8 @@ extern "C" int gacq_requant_open(gacq_ctx* ctx, const gacq_requant_cfg* cfg, con
   if (!out) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_requant_open: NULL argument");
   *out = nullptr;
   const int rc = gacq_requant_check(cfg, gains, thresholds, 0, 0, 0, 0);
-  if (rc < 0) return set_error(ctx, rc, "%s", gacq_last_error(nullptr));
-  gacq_requant* h = new gacq_requant;
+  if (rc < 0) return st_forward(ctx, rc);
+  std::unique_ptr<gacq_requant> h(new gacq_requant);
   h->ctx = ctx;
   h->cfg = *cfg;
   h->gains.assign(gains, gains + cfg->ngains);
@@ -413,28 +406,16 @@ extern "C" int gacq_requant_open(gacq_ctx* ctx, const gacq_requant_cfg* cfg, con
   std::copy(h->gains.begin(), h->gains.end(), g.begin());
   {
     GACQ_DEVICE(ctx);
-    hipError_t e = hipMalloc(&h->dev, words * 8 + kRqMaxGains * sizeof(float));
-    // the uploads are blocking copies from pageable memory: they have landed when the call returns
-    if (e == hipSuccess) e = hipMemcpy(h->dev, h->thresholds.data(), kRqMaxGains * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy((uint64_t*)h->dev + words, g.data(), kRqMaxGains * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      if (h->dev) (void)hipFree(h->dev);
-      delete h;
-      return set_error(ctx, GACQ_ERR_HIP, "gacq_requant_open: %s", hipGetErrorString(e));
-    }
+    hipError_t e = h->dev.alloc(ctx, words * 8 + kRqMaxGains * sizeof(float));
+    if (e == hipSuccess) e = h->dev.upload(0, h->thresholds.data(), kRqMaxGains * 8);
+    if (e == hipSuccess) e = h->dev.upload(words * 8, g.data(), kRqMaxGains * sizeof(float));
+    if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_requant_open: %s", hipGetErrorString(e));
   }
-  *out = h;
+  *out = h.release();
   return GACQ_OK;
 }
 
-extern "C" void gacq_requant_close(gacq_requant* h) {
-  if (!h) return;
-  if (h->dev) {
-    DeviceGuard guard(h->ctx->device);
-    (void)hipFree(h->dev);
-  }
-  delete h;
-}
+extern "C" void gacq_requant_close(gacq_requant* h) { delete h; }
 
 extern "C" int gacq_requant_run_dev(gacq_requant* h, const void* d_in, long long in_first, long long in_count, long long out_first, long long n_out,
                                     void* d_out, void* d_stats, void* d_gain_index) {
@@ -443,8 +424,8 @@ extern "C" int gacq_requant_run_dev(gacq_requant* h, const void* d_in, long long
   if (!d_in || !d_out) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_requant_run_dev: NULL argument");
   // everything is checked before anything is launched
   const gacq_requant_cfg& c = h->cfg;
-  const int rc = gacq_requant_check(&c, h->gains.data(), h->thresholds.data(), in_first, in_count, out_first, n_out);
-  if (rc < 0) return set_error(ctx, rc, "%s", gacq_last_error(nullptr));
+  int rc = gacq_requant_check(&c, h->gains.data(), h->thresholds.data(), in_first, in_count, out_first, n_out);
+  if (rc < 0) return st_forward(ctx, rc);
   const bool in16 = c.in_bits == 16;
   if (in16 && (uintptr_t)d_in % 2u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_requant_run_dev: int16 input must be 2-byte aligned");
   if (c.container == GACQ_INGEST_S16 && (uintptr_t)d_out % 2u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_requant_run_dev: int16 output must be 2-byte aligned");
@@ -454,9 +435,9 @@ extern "C" int gacq_requant_run_dev(gacq_requant* h, const void* d_in, long long
   const int form = form_of(c), run = run_of(form), esz = in16 ? 2 : 1;
   const long long Lb = c.block, W = c.window, out_end = out_first + n_out;
   const size_t words = kRqMaxGains + (size_t)(kRqChunkBlocks + kRqMaxWindow);
-  const unsigned long long* dT = (const unsigned long long*)h->dev;
-  unsigned long long* dP = (unsigned long long*)h->dev + kRqMaxGains;
-  const float* dG = (const float*)((const uint64_t*)h->dev + words);
+  const unsigned long long* dT = (const unsigned long long*)h->dev.p;
+  unsigned long long* dP = (unsigned long long*)h->dev.p + kRqMaxGains;
+  const float* dG = (const float*)((const uint64_t*)h->dev.p + words);
   unsigned long long enc = 0;
   if (c.container == GACQ_INGEST_PACKED)
     for (int q = 0; q < (1 << c.bits); q++) enc |= (unsigned long long)c.enc[q] << (4 * q);
@@ -482,8 +463,7 @@ extern "C" int gacq_requant_run_dev(gacq_requant* h, const void* d_in, long long
     const unsigned pgrid = (unsigned)std::min<long long>(npass, (long long)kRqMaxGrid);
     if (in16) hipLaunchKernelGGL((requant_power_kernel<true>), dim3(pgrid), dim3(kRqBlock), 0, ctx->stream, p);
     else hipLaunchKernelGGL((requant_power_kernel<false>), dim3(pgrid), dim3(kRqBlock), 0, ctx->stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_requant_run_dev: launch failed: %s", hipGetErrorString(e));
+    if ((rc = st_launched(ctx, "gacq_requant_run_dev")) < 0) return rc;
     // ---- the outputs o .. o_end - 1
     RqQuantArgs a;
     a.ncomp = (int)(2 * (o_end - o));
@@ -509,8 +489,7 @@ extern "C" int gacq_requant_run_dev(gacq_requant* h, const void* d_in, long long
     const unsigned grid = std::min((unsigned)ntiles, kRqMaxGrid);
     if (in16) launch_quantize<true>(form, grid, ctx->stream, a);
     else launch_quantize<false>(form, grid, ctx->stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_requant_run_dev: launch failed: %s", hipGetErrorString(e));
+    if ((rc = st_launched(ctx, "gacq_requant_run_dev")) < 0) return rc;
     o = o_end;
   }
   return GACQ_OK;

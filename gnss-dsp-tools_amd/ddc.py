@@ -27,7 +27,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import _native as nat
-from . import acquire, ingest, rawfile
+from . import ingest, rawfile, streaming
 
 MAX_DECIM, MAX_TAPS = 64, 513
 MAX_TAP_SUM = 65536
@@ -144,67 +144,31 @@ class Band:
 
 def _device_iq(engine, data):
     """flat uint8 CUDA tensor (any byte offset) of a flat int8 / uint8 CUDA tensor or a bytes-like object of int8 pairs"""
-    torch = nat.require_torch()
-    if torch.is_tensor(data):
-        if not data.is_cuda or data.dtype not in (torch.uint8, torch.int8) or data.dim() != 1:
-            raise ValueError("data must be a flat int8 or uint8 CUDA tensor or a bytes-like object")
-        data = data if data.is_contiguous() else data.contiguous()
-        return data.view(torch.uint8)
-    h = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
-    return torch.from_numpy(np.array(h, copy=True)).to("cuda:%d" % engine.device)
+    return streaming.device_flat(engine, data, ("uint8", "int8"), "data must be a flat int8 or uint8 CUDA tensor or a bytes-like object", "uint8")
 
 
-class Converter:
+class Converter(streaming.Handle):
     """The open device side of one band at one sample rate (gacq_ddc_open: the table and the taps are uploaded once); run() is one
     asynchronous launch on torch's current stream.  Closed with its engine at the latest."""
+    _close, _what = "gacq_ddc_close", "converter"
 
     def __init__(self, engine, band, fs):
-        self.engine, self.band, self.fs = engine, band, float(fs)
+        self.band, self.fs = band, float(fs)
         if not self.fs > 0.0 or not math.isfinite(self.fs):
             raise ValueError("the sample rate must be positive and finite")
         self.taps = np.ascontiguousarray(band.taps_for(self.fs), dtype=np.int32)
         self.cfg = DdcCfg(dphase=band.dphase(self.fs), decim=band.D)
-        h = ctypes.c_void_p()
-        nat.check(nat.lib.gacq_ddc_open(engine._ctx, ctypes.addressof(self.cfg), ctypes.c_void_p(self.taps.ctypes.data), len(self.taps), ctypes.byref(h)),
-                  engine._ctx)
-        self._h = h
-        engine._live.add(self)                      # Engine.close() closes what lives on its context
+        self._open(engine, nat.lib.gacq_ddc_open, ctypes.addressof(self.cfg), ctypes.c_void_p(self.taps.ctypes.data), len(self.taps))
 
     def run(self, d, in_first, out_first, n_out, gain, dtype="int8"):
         """outputs out_first .. out_first + n_out - 1 of the recording whose samples in_first .. are the int8 pairs of the flat uint8
         CUDA tensor d"""
-        torch = nat.require_torch()
-        if dtype not in ("int8", "complex64"):
-            raise ValueError("dtype must be 'int8' or 'complex64', not %r" % (dtype,))
-        if not self._h:
-            raise ValueError("the converter is closed")
-        cplx = dtype == "complex64"
         n_out = int(n_out)
-        out = torch.empty(max(n_out, 0) * (1 if cplx else 2), dtype=torch.complex64 if cplx else torch.int8, device=d.device)
-        if d.numel() == 0 and n_out == 0:
-            return out
-        self.engine.use_torch_stream(d.device)
-        # an output without elements has no address to speak of: the call still makes its checks
-        nat.check(nat.lib.gacq_ddc_run_dev(self._h, ctypes.c_void_p(d.data_ptr() if d.numel() else 0), int(in_first), d.numel() // 2, int(out_first), n_out,
-                                           float(gain), int(cplx), ctypes.c_void_p(out.data_ptr() if out.numel() else d.data_ptr())), self.engine._ctx)
-        return out
-
-    def close(self):
-        if self._h:
-            nat.lib.gacq_ddc_close(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        cplx, out = streaming.iq_out(n_out, dtype, d.device)
+        self._check_open()
+        return streaming.launch(self.engine, [d], d.numel(), out, n_out, lambda src, dst: nat.check(
+            nat.lib.gacq_ddc_run_dev(self._h, ctypes.c_void_p(src[0]), int(in_first), d.numel() // 2, int(out_first), n_out, float(gain), int(cplx),
+                                     ctypes.c_void_p(dst)), self.engine._ctx))
 
 
 def convert(engine, band, fs, data, gain, in_first=0, out_first=None, n_out=None, dtype="int8"):
@@ -236,7 +200,7 @@ def auto_window(band):
     return (AUTO_SAMPLES - 1) * band.D + band.H + 1
 
 
-class Splitter:
+class Splitter(streaming.Chunks):
     """One recording fed chunk by chunk into several bands: feed(chunk) uploads the chunk once, launches every band on it and returns
     each band's output samples that the chunk completes; the concatenation of what the calls return for a band is what one convert()
     of the whole recording gives.  The input tail that some band's next output still needs, and the byte of a sample that a chunk
@@ -248,27 +212,12 @@ class Splitter:
         if len(self.gains) != len(self.bands) or not self.bands:
             raise ValueError("one gain per band, and at least one band")
         self.convs = [Converter(engine, b, fs) for b in self.bands]
-        self.in_first = 0                           # absolute index of the first input sample of the kept tail
-        self.next_out = [0] * len(self.bands)       # every band's next output sample
-        self._tail = None
+        super().__init__(16, lambda in_first, in_count: [sum(b.out_range(in_first, in_count)) for b in self.bands],
+                         lambda ds, in_first, in_count, out_first, n_out, k: self.convs[k].run(ds[0], in_first, out_first, n_out, self.gains[k], dtype),
+                         lambda nexts: min(b.first_needed(m) for b, m in zip(self.bands, nexts)), outputs=len(self.bands))
 
     def feed(self, chunk):
-        torch = nat.require_torch()
-        d = _device_iq(self.engine, chunk)
-        if self._tail is not None and self._tail.numel():
-            d = torch.cat([self._tail, d])
-        in_count = d.numel() // 2
-        outs = []
-        for k, (band, conv) in enumerate(zip(self.bands, self.convs)):
-            first, count = band.out_range(self.in_first, in_count)
-            n_out = max(0, first + count - self.next_out[k])
-            outs.append(conv.run(d[:2 * in_count], self.in_first, self.next_out[k], n_out, self.gains[k], self.dtype))
-            self.next_out[k] += n_out
-        need = min(b.first_needed(m) for b, m in zip(self.bands, self.next_out))
-        keep = max(self.in_first, min(need, self.in_first + in_count))
-        self._tail = d[2 * (keep - self.in_first):].clone()
-        self.in_first = keep
-        return outs
+        return self.feed_all([_device_iq(self.engine, chunk)])
 
     def close(self):
         for c in self.convs:
@@ -306,41 +255,25 @@ def split_file(engine, bands, fs, fin, fouts, gain=None, target_rms=TARGET_RMS, 
     if len(bands) != len(fouts) or not bands:
         raise ValueError("one output per band, and at least one band")
     gains = None if gain is None else ([float(g) for g in gain] if np.ndim(gain) else [float(gain)] * len(bands))
-    sp, n = None, [0] * len(bands)
-    per = 2 if dtype == "int8" else 1
+    sp = None
     window = 0 if gains is not None else max(auto_window(b) for b in bands)
-    held = []                                       # automatic gain: the pieces read until they hold every band's window (or the file ends)
 
-    def feed(d):
-        for k, out in enumerate(sp.feed(d)):
-            n[k] += out.numel() // per
-            fouts[k].write(out.cpu().numpy().tobytes())
-
-    def start():
+    def start(held):
         nonlocal sp, gains
+        if len(held) == 1:                          # one piece holds the window (or all there is): uploaded once, it serves the gain and the bands
+            held[0] = _device_iq(engine, held[0])
         if gains is None:
             first = held[0] if len(held) == 1 else np.concatenate(held)[:2 * window]
             gains = [auto_gain(engine, b, fs, first[:2 * auto_window(b)], target_rms) for b in bands]
         sp = Splitter(engine, bands, fs, gains, dtype)
-        for d in held:
-            feed(d)
-        held.clear()
+        return sp.feed
 
-    try:
-        for piece in rawfile.read_pieces(fin, 2, piece_bytes):
-            if sp is None:
-                # a first piece that holds the window is uploaded once and serves the gain and the bands; shorter pieces wait on the host
-                held.append(_device_iq(engine, piece.view(np.uint8)) if (not held and len(piece) >= 2 * window) else piece.view(np.uint8))
-                if sum(len(h) if isinstance(h, np.ndarray) else h.numel() for h in held) >= 2 * window:
-                    start()
-            else:
-                feed(_device_iq(engine, piece.view(np.uint8)))
-        if sp is None and held:
-            start()
+    try:                                            # pieces shorter than the window wait on the host
+        n = streaming.pump(rawfile.read_pieces(fin, 2, piece_bytes), start, fouts, 2 if dtype == "int8" else 1, 2 * window)
     finally:
         if sp is not None:
             sp.close()
-    if sp is None:
+    if n is None:
         raise ValueError("the input holds no whole sample")
     return gains, n
 
@@ -378,7 +311,7 @@ def parse(argv):
     bad = None
     if not (a.fs > 0.0 and math.isfinite(a.fs)) or not math.isfinite(a.coffset):
         bad = "need a positive, finite FS and a finite COFFSET"
-    elif (a.gain is not None and not (a.gain > 0.0 and math.isfinite(a.gain))) or not (a.target_rms > 0.0 and math.isfinite(a.target_rms)):
+    elif (a.gain is not None and not streaming.positive_finite(a.gain)) or not streaming.positive_finite(a.target_rms):
         bad = "need a positive, finite --gain / --target-rms"
     elif a.cutoff is not None and not 0.0 < a.cutoff < 0.5 * a.fs:
         bad = "--cutoff must lie inside (0, FS / 2)"
@@ -402,36 +335,16 @@ def report_line(band, fs, coffset, gain, samples):
 
 def run(argv, out=None, piece_bytes=rawfile.PIECE_BYTES):
     a, bands, names = parse(argv)
-    to_stdout = names == ["-"]
-    if out is None:
-        out = sys.stderr if to_stdout else sys.stdout
-    fin = sys.stdin.buffer if a.input_filename == "-" else open(a.input_filename, "rb")
-    fouts = [sys.stdout.buffer] if to_stdout else [open(o, "wb") for o in names]
-    eng = acquire.Engine(a.device)
-    try:
-        gains, n = split_file(eng, bands, a.fs, fin, fouts, a.gain, a.target_rms, "complex64" if a.complex64 else "int8", piece_bytes)
-        for f in fouts:
-            f.flush()
-    finally:
-        eng.close()
-        if fin is not sys.stdin.buffer:
-            fin.close()
-        if not to_stdout:
-            for f in fouts:
-                f.close()
+    with streaming.shell(a.device, [a.input_filename], names, report=out) as sh:
+        gains, n = split_file(sh.engine, bands, a.fs, sh.fins[0], sh.fouts, a.gain, a.target_rms, "complex64" if a.complex64 else "int8", piece_bytes)
     lines = [report_line(b, a.fs, a.coffset, g, k) for b, g, k in zip(bands, gains, n)]
     for line in lines:
-        print(line, file=out)
+        print(line, file=sh.report)
     return lines
 
 
 def main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
-    if not argv or argv[0] in ("-h", "--help"):
-        print(__doc__)
-        return 0
-    run(argv)
-    return 0
+    return streaming.main(argv, __doc__, run)
 
 
 if __name__ == "__main__":

@@ -25,7 +25,7 @@ import sys
 import numpy as np
 
 from . import _native as nat
-from . import acquire, rawfile
+from . import rawfile, streaming
 
 S8, U8, S16, F32, PACKED = range(5)                 # GACQ_INGEST_*
 CONTAINERS = {"s8": S8, "u8": U8, "s16": S16, "f32": F32}
@@ -107,40 +107,25 @@ def as_format(fmt):
 
 def _device_bytes(engine, data):
     """uint8 CUDA tensor (any byte offset) of a uint8 CUDA tensor or a bytes-like object"""
-    torch = nat.require_torch()
-    if torch.is_tensor(data):
-        if not data.is_cuda or data.dtype != torch.uint8 or data.dim() != 1:
-            raise ValueError("data must be a flat uint8 CUDA tensor or a bytes-like object")
-        return data if data.is_contiguous() else data.contiguous()
-    h = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
-    return torch.from_numpy(np.array(h, copy=True)).to("cuda:%d" % engine.device)
+    return streaming.device_flat(engine, data, ("uint8",), "data must be a flat uint8 CUDA tensor or a bytes-like object")
 
 
 def convert(engine, fmt, data, gain, in_first=0, out_first=None, n_out=None, dtype="int8"):
     """Output samples out_first .. out_first + n_out - 1 of the recording whose input samples in_first .. are at `data` (a flat uint8
     CUDA tensor or a bytes-like object): a flat int8 CUDA tensor [2 n_out] of interleaved I/Q, or complex64 [n_out].  By default
     every output sample the data supports.  Asynchronous on torch's current stream."""
-    torch = nat.require_torch()
     fmt = as_format(fmt)
-    if dtype not in ("int8", "complex64"):
-        raise ValueError("dtype must be 'int8' or 'complex64', not %r" % (dtype,))
     d = _device_bytes(engine, data)
     in_first = int(in_first)
     in_count = fmt.samples(d.numel())
     first, count = fmt.out_range(in_first, in_count)
     out_first = first if out_first is None else int(out_first)
     n_out = max(0, first + count - out_first) if n_out is None else int(n_out)
-    cplx = dtype == "complex64"
-    out = torch.empty(max(n_out, 0) * (1 if cplx else 2), dtype=torch.complex64 if cplx else torch.int8, device=d.device)
-    if d.numel() == 0 and n_out == 0:
-        return out
-    engine.use_torch_stream(d.device)
+    cplx, out = streaming.iq_out(n_out, dtype, d.device)
     st = fmt.struct()
-    # an output without elements has no address to speak of: the call still makes its checks
-    nat.check(nat.lib.gacq_ingest_dev(engine._ctx, ctypes.addressof(st), ctypes.c_void_p(d.data_ptr() if d.numel() else 0), in_first, in_count,
-                                      out_first, n_out, float(gain), int(cplx), ctypes.c_void_p(out.data_ptr() if out.numel() else d.data_ptr())),
-              engine._ctx)
-    return out
+    return streaming.launch(engine, [d], d.numel(), out, n_out, lambda src, dst: nat.check(
+        nat.lib.gacq_ingest_dev(engine._ctx, ctypes.addressof(st), ctypes.c_void_p(src[0]), in_first, in_count, out_first, n_out, float(gain), int(cplx),
+                                ctypes.c_void_p(dst)), engine._ctx))
 
 
 def rms_gain(u, target_rms=TARGET_RMS):
@@ -164,7 +149,7 @@ def auto_gain(engine, fmt, first_piece, target_rms=TARGET_RMS):
     return rms_gain(convert(engine, fmt, d, 1.0, 0, 0, p, "complex64").cpu().numpy(), target_rms)
 
 
-class Ingest:
+class Ingest(streaming.Chunks):
     """A recording fed chunk by chunk: feed(chunk) returns the output samples the chunk completes, and the concatenation of what the
     calls return is what one convert() of the whole recording gives.  What the next call still needs stays on the device: the bytes of
     a sample (or of a byte of packed codes) that the chunk cut, and in real mode the input tail under the next outputs' supports; the
@@ -173,48 +158,33 @@ class Ingest:
 
     def __init__(self, engine, fmt, gain, dtype="int8"):
         self.engine, self.fmt, self.gain, self.dtype = engine, as_format(fmt), float(gain), dtype
-        self.in_first = 0            # absolute index of the first input sample of the kept tail
-        self.next_out = 0            # the next output sample
-        self._tail = None
+        fmt = self.fmt
+        # real mode keeps the tail from the first input sample the next output needs, moved down to a multiple of 16 samples: a byte
+        # boundary in every format, and a 16-byte boundary of 8-bit real input
+        # (I/Q: whole samples are whole bytes, or whole bytes hold whole samples, so the end of the whole samples is on a byte boundary)
+        super().__init__(fmt.sample_bits, lambda in_first, in_count: sum(fmt.out_range(in_first, in_count)),
+                         lambda ds, in_first, in_count, out_first, n_out, k: convert(engine, fmt, ds[0], self.gain, in_first, out_first, n_out, dtype),
+                         lambda out: (2 * out - HALF) // 16 * 16 if fmt.real else out)
 
     def feed(self, chunk):
-        torch = nat.require_torch()
-        d = _device_bytes(self.engine, chunk)
-        if self._tail is not None and self._tail.numel():
-            d = torch.cat([self._tail, d])
-        fmt = self.fmt
-        in_count = fmt.samples(d.numel())
-        first, count = fmt.out_range(self.in_first, in_count)
-        n_out = max(0, first + count - self.next_out)
-        out = convert(self.engine, fmt, d, self.gain, self.in_first, self.next_out, n_out, self.dtype)
-        self.next_out += n_out
-        # the first input sample the next output needs, moved down to a multiple of 16 samples: a byte boundary in every format, and
-        # a 16-byte boundary of 8-bit real input
-        # (I/Q: whole samples are whole bytes, or whole bytes hold whole samples, so in_first + in_count is on a byte boundary)
-        keep = self.in_first + in_count if not fmt.real else max(self.in_first, (2 * self.next_out - HALF) // 16 * 16)
-        at = (keep - self.in_first) * fmt.sample_bits // 8
-        self._tail = d[at:].clone()
-        self.in_first = keep
-        return out
+        return self.feed_all([_device_bytes(self.engine, chunk)])
 
 
 def convert_file(engine, fmt, fin, fout, gain=None, target_rms=TARGET_RMS, dtype="int8", piece_bytes=rawfile.PIECE_BYTES):
     """Convert the open binary file fin into fout piece by piece; gain None: the automatic gain of the first piece.  (gain, samples)."""
     fmt = as_format(fmt)
-    unit = max(1, fmt.sample_bits // 8)
-    ing, n = None, 0
-    for piece in rawfile.read_pieces(fin, unit, piece_bytes):
-        piece = piece.view(np.uint8)
-        if ing is None:
-            if gain is None:                    # 16 bytes per output sample and 64 more hold 65536 output samples of every format
-                gain = auto_gain(engine, fmt, piece[:AUTO_SAMPLES * 16 + 64], target_rms)
-            ing = Ingest(engine, fmt, gain, dtype)
-        out = ing.feed(piece)
-        n += out.numel() // (2 if dtype == "int8" else 1)
-        fout.write(out.cpu().numpy().tobytes())
-    if ing is None:
+
+    def start(held):
+        nonlocal gain
+        if gain is None:                        # 16 bytes per output sample and 64 more hold 65536 output samples of every format
+            gain = auto_gain(engine, fmt, held[0][:AUTO_SAMPLES * 16 + 64], target_rms)
+        ing = Ingest(engine, fmt, gain, dtype)
+        return lambda piece: [ing.feed(piece)]
+
+    n = streaming.pump(rawfile.read_pieces(fin, max(1, fmt.sample_bits // 8), piece_bytes), start, [fout], 2 if dtype == "int8" else 1)
+    if n is None:
         raise ValueError("the input holds no whole sample")
-    return float(gain), n
+    return float(gain), n[0]
 
 
 def build_parser():
@@ -249,7 +219,7 @@ def parse(argv):
         fmt = Format(a.format, real=a.real, conj=a.conj, msb_first=not a.lsb_first, lut=lut)
     except ValueError as e:
         raise SystemExit("ingest: %s" % e)
-    if not a.fs > 0.0 or (a.gain is not None and not (a.gain > 0.0 and math.isfinite(a.gain))) or not (a.target_rms > 0.0 and math.isfinite(a.target_rms)):
+    if not a.fs > 0.0 or (a.gain is not None and not streaming.positive_finite(a.gain)) or not streaming.positive_finite(a.target_rms):
         raise SystemExit("ingest: need FS > 0 and a positive, finite --gain / --target-rms")
     return a, fmt
 
@@ -261,33 +231,15 @@ def report_line(fmt, fs, coffset, gain, samples):
 
 def run(argv, out=None, piece_bytes=rawfile.PIECE_BYTES):
     a, fmt = parse(argv)
-    to_stdout = a.output_filename == "-"
-    if out is None:
-        out = sys.stderr if to_stdout else sys.stdout
-    fin = sys.stdin.buffer if a.input_filename == "-" else open(a.input_filename, "rb")
-    fout = sys.stdout.buffer if to_stdout else open(a.output_filename, "wb")
-    eng = acquire.Engine(a.device)
-    try:
-        gain, n = convert_file(eng, fmt, fin, fout, a.gain, a.target_rms, "complex64" if a.complex64 else "int8", piece_bytes)
-        fout.flush()
-    finally:
-        eng.close()
-        if fin is not sys.stdin.buffer:
-            fin.close()
-        if not to_stdout:
-            fout.close()
+    with streaming.shell(a.device, [a.input_filename], [a.output_filename], report=out) as sh:
+        gain, n = convert_file(sh.engine, fmt, sh.fins[0], sh.fouts[0], a.gain, a.target_rms, "complex64" if a.complex64 else "int8", piece_bytes)
     line = report_line(fmt, a.fs, a.coffset, gain, n)
-    print(line, file=out)
+    print(line, file=sh.report)
     return line
 
 
 def main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
-    if not argv or argv[0] in ("-h", "--help"):
-        print(__doc__)
-        return 0
-    run(argv)
-    return 0
+    return streaming.main(argv, __doc__, run)
 
 
 if __name__ == "__main__":

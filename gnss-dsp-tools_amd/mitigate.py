@@ -25,7 +25,7 @@ import sys
 import numpy as np
 
 from . import _native as nat
-from . import acquire, ingest, rawfile
+from . import ingest, rawfile, streaming
 
 MAX_HOLD, MAX_GUARD = 64, 8
 AUTO_SAMPLES = ingest.AUTO_SAMPLES
@@ -79,16 +79,11 @@ class Stats:
 def _device_input(engine, data, in_complex64):
     """(tensor, complex64?) : a flat int8 or complex64 CUDA tensor as it is; a uint8 CUDA tensor or a bytes-like object as the bytes of
     int8 pairs, or of complex64 samples with in_complex64"""
+    d = streaming.device_flat(engine, data, ("int8", "uint8", "complex64"), "data must be a flat int8, uint8 or complex64 CUDA tensor or a bytes-like object")
     torch = nat.require_torch()
     if torch.is_tensor(data):
-        if not data.is_cuda or data.dim() != 1 or data.dtype not in (torch.int8, torch.uint8, torch.complex64):
-            raise ValueError("data must be a flat int8, uint8 or complex64 CUDA tensor or a bytes-like object")
-        d = data if data.is_contiguous() else data.contiguous()
         return d, (d.dtype == torch.complex64 or (d.dtype == torch.uint8 and bool(in_complex64)))
-    if isinstance(data, np.ndarray) and data.dtype == np.complex64:
-        in_complex64 = True
-    h = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
-    return torch.from_numpy(np.array(h, copy=True)).to("cuda:%d" % engine.device), bool(in_complex64)
+    return d, bool(in_complex64) or (isinstance(data, np.ndarray) and data.dtype == np.complex64)
 
 
 def _count(d, cplx):
@@ -101,16 +96,13 @@ def apply(engine, cfg, data, gain, in_first=0, out_first=None, n_out=None, dtype
     interleaved I/Q, or complex64 [n_out]; with stats, (that, Stats).  By default every output sample the data supports.
     Asynchronous on torch's current stream (reading the statistics waits for it)."""
     torch = nat.require_torch()
-    if dtype not in ("int8", "complex64"):
-        raise ValueError("dtype must be 'int8' or 'complex64', not %r" % (dtype,))
     d, in_c = _device_input(engine, data, in_complex64)
     in_first = int(in_first)
     in_count = _count(d, in_c)
     first, count = cfg.out_range(in_first, in_count)
     out_first = first if out_first is None else int(out_first)
     n_out = max(0, first + count - out_first) if n_out is None else int(n_out)
-    cplx = dtype == "complex64"
-    out = torch.empty(max(n_out, 0) * (1 if cplx else 2), dtype=torch.complex64 if cplx else torch.int8, device=d.device)
+    cplx, out = streaming.iq_out(n_out, dtype, d.device)
     st = fb = None
     if stats:
         nfr = 0
@@ -119,13 +111,11 @@ def apply(engine, cfg, data, gain, in_first=0, out_first=None, n_out=None, dtype
             nfr = max(0, (out_first + n_out - 1) // h - (-(-out_first // h)) + 1)
         st = torch.zeros(3, dtype=torch.int64, device=d.device)
         fb = torch.zeros(max(nfr, 1), dtype=torch.int32, device=d.device)
-    if not (d.numel() == 0 and n_out == 0):
-        engine.use_torch_stream(d.device)
-        c = cfg.struct()
-        nat.check(nat.lib.gacq_mitigate_dev(engine._ctx, ctypes.addressof(c), ctypes.c_void_p(d.data_ptr() if d.numel() else 0), int(in_c), in_first,
-                                            in_count, out_first, n_out, float(gain), int(cplx),
-                                            ctypes.c_void_p(out.data_ptr() if out.numel() else d.data_ptr()),
-                                            ctypes.c_void_p(st.data_ptr() if stats else 0), ctypes.c_void_p(fb.data_ptr() if stats else 0)), engine._ctx)
+    c = cfg.struct()
+    streaming.launch(engine, [d], d.numel(), out, n_out, lambda src, dst: nat.check(
+        nat.lib.gacq_mitigate_dev(engine._ctx, ctypes.addressof(c), ctypes.c_void_p(src[0]), int(in_c), in_first, in_count, out_first, n_out, float(gain),
+                                  int(cplx), ctypes.c_void_p(dst), ctypes.c_void_p(st.data_ptr() if stats else 0),
+                                  ctypes.c_void_p(fb.data_ptr() if stats else 0)), engine._ctx))
     if not stats:
         return out
     s = st.cpu().numpy()
@@ -143,7 +133,7 @@ def auto_gain(engine, cfg, first_piece, target_rms=TARGET_RMS, in_complex64=Fals
     return ingest.rms_gain(apply(engine, cfg, d, 1.0, 0, 0, p, "complex64", in_complex64=in_c).cpu().numpy(), target_rms)
 
 
-class Mitigate:
+class Mitigate(streaming.Chunks):
     """A recording fed chunk by chunk (bytes or uint8 / int8 / complex64 CUDA tensors): feed(chunk) returns the output samples the
     chunk completes, and the concatenation of what the calls return is what one apply() of the whole recording gives.  The input tail
     under the next output block's support, and the bytes of a sample that a chunk cut, stay on the device.  blanked, frames and bins
@@ -151,49 +141,38 @@ class Mitigate:
 
     def __init__(self, engine, cfg, gain, dtype="int8", in_complex64=False):
         self.engine, self.cfg, self.gain, self.dtype, self.in_complex64 = engine, cfg, float(gain), dtype, bool(in_complex64)
-        self.in_first = 0            # absolute index of the first input sample of the kept tail
-        self.next_out = 0            # the next output sample
         self.blanked = self.frames = self.bins = 0
-        self._tail = None
+        super().__init__(64 if self.in_complex64 else 16, lambda in_first, in_count: sum(cfg.out_range(in_first, in_count)), self._run, cfg.first_needed)
+
+    def _run(self, ds, in_first, in_count, out_first, n_out, k):
+        x = ds[0] if self.in_complex64 else ds[0].view(nat.require_torch().int8)
+        out, st = apply(self.engine, self.cfg, x, self.gain, in_first, out_first, n_out, self.dtype, True, self.in_complex64)
+        self.blanked, self.frames, self.bins = self.blanked + st.blanked, self.frames + st.frames, self.bins + st.bins
+        return out
 
     def feed(self, chunk):
         torch = nat.require_torch()
         d, _ = _device_input(self.engine, chunk, self.in_complex64)
-        d = (torch.view_as_real(d).reshape(-1) if d.dtype.is_complex else d).view(torch.uint8)
-        if self._tail is not None and self._tail.numel():
-            d = torch.cat([self._tail, d])
-        unit = 8 if self.in_complex64 else 2
-        in_count = d.numel() // unit
-        first, count = self.cfg.out_range(self.in_first, in_count)
-        n_out = max(0, first + count - self.next_out)
-        whole = d[:in_count * unit]
-        out, st = apply(self.engine, self.cfg, whole.view(torch.int8) if not self.in_complex64 else whole, self.gain, self.in_first, self.next_out,
-                        n_out, self.dtype, True, self.in_complex64)
-        self.next_out += n_out
-        self.blanked, self.frames, self.bins = self.blanked + st.blanked, self.frames + st.frames, self.bins + st.bins
-        keep = max(self.in_first, min(self.cfg.first_needed(self.next_out), self.in_first + in_count))
-        self._tail = d[(keep - self.in_first) * unit:].clone()
-        self.in_first = keep
-        return out
+        return self.feed_all([(torch.view_as_real(d).reshape(-1) if d.dtype.is_complex else d).view(torch.uint8)])
 
 
 def mitigate_file(engine, cfg, fin, fout, gain=None, target_rms=TARGET_RMS, dtype="int8", in_complex64=False, piece_bytes=rawfile.PIECE_BYTES):
     """Filter the open binary file fin into fout piece by piece; gain None: the automatic gain of the first piece.
     (gain, samples, Mitigate with the totals)."""
     unit = 8 if in_complex64 else 2
-    mit, n = None, 0
-    for piece in rawfile.read_pieces(fin, unit, piece_bytes):
-        piece = piece.view(np.uint8)
-        if mit is None:
-            if gain is None:                    # the first 65536 outputs need at most 65536 + 3 N / 2 + 2 hold inputs
-                gain = auto_gain(engine, cfg, piece[:(AUTO_SAMPLES + 2 * 4096 + 2 * MAX_HOLD) * unit], target_rms, in_complex64)
-            mit = Mitigate(engine, cfg, gain, dtype, in_complex64)
-        out = mit.feed(piece)
-        n += out.numel() // (2 if dtype == "int8" else 1)
-        fout.write(out.cpu().numpy().tobytes())
-    if mit is None:
+    mit = None
+
+    def start(held):
+        nonlocal gain, mit
+        if gain is None:                        # the first 65536 outputs need at most 65536 + 3 N / 2 + 2 hold inputs
+            gain = auto_gain(engine, cfg, held[0].view(np.uint8)[:(AUTO_SAMPLES + 2 * 4096 + 2 * MAX_HOLD) * unit], target_rms, in_complex64)
+        mit = Mitigate(engine, cfg, gain, dtype, in_complex64)
+        return lambda piece: [mit.feed(piece.view(np.uint8))]
+
+    n = streaming.pump(rawfile.read_pieces(fin, unit, piece_bytes), start, [fout], 2 if dtype == "int8" else 1)
+    if n is None:
         raise ValueError("the input holds no whole sample")
-    return float(gain), n, mit
+    return float(gain), n[0], mit
 
 
 def build_parser():
@@ -230,7 +209,7 @@ def parse(argv):
         bad = "--ratio must be finite and above 1"
     elif not nfft and a.blank is None:
         bad = "--no-excise needs --blank: both stages would be off"
-    elif (a.gain is not None and not (a.gain > 0.0 and math.isfinite(a.gain))) or not (a.target_rms > 0.0 and math.isfinite(a.target_rms)):
+    elif (a.gain is not None and not streaming.positive_finite(a.gain)) or not streaming.positive_finite(a.target_rms):
         bad = "need a positive, finite --gain / --target-rms"
     if bad:
         raise SystemExit("mitigate: %s" % bad)
@@ -244,33 +223,16 @@ def report_line(cfg, gain, samples, blanked, frames, bins):
 
 def run(argv, out=None, piece_bytes=rawfile.PIECE_BYTES):
     a, cfg = parse(argv)
-    to_stdout = a.output_filename == "-"
-    if out is None:
-        out = sys.stderr if to_stdout else sys.stdout
-    fin = sys.stdin.buffer if a.input_filename == "-" else open(a.input_filename, "rb")
-    fout = sys.stdout.buffer if to_stdout else open(a.output_filename, "wb")
-    eng = acquire.Engine(a.device)
-    try:
-        gain, n, mit = mitigate_file(eng, cfg, fin, fout, a.gain, a.target_rms, "complex64" if a.complex64 else "int8", a.in_complex64, piece_bytes)
-        fout.flush()
-    finally:
-        eng.close()
-        if fin is not sys.stdin.buffer:
-            fin.close()
-        if not to_stdout:
-            fout.close()
+    with streaming.shell(a.device, [a.input_filename], [a.output_filename], report=out) as sh:
+        gain, n, mit = mitigate_file(sh.engine, cfg, sh.fins[0], sh.fouts[0], a.gain, a.target_rms, "complex64" if a.complex64 else "int8", a.in_complex64,
+                                     piece_bytes)
     line = report_line(cfg, gain, n, mit.blanked, mit.frames, mit.bins)
-    print(line, file=out)
+    print(line, file=sh.report)
     return line
 
 
 def main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
-    if not argv or argv[0] in ("-h", "--help"):
-        print(__doc__)
-        return 0
-    run(argv)
-    return 0
+    return streaming.main(argv, __doc__, run)
 
 
 if __name__ == "__main__":

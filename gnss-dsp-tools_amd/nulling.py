@@ -19,13 +19,13 @@ of unequal length end at the shortest; a recording shorter than W blocks gives n
 tests/nulling_oracle.py restates it in numpy."""
 import argparse
 import ctypes
-import math
 import sys
 
 import numpy as np
 
 from . import _native as nat
-from . import acquire, ingest, rawfile
+from . import ingest, rawfile, streaming
+from .streaming import first_needed, out_end, owned_blocks      # the block / window algebra, part of this module as before
 
 MAX_ANTENNAS, MAX_WINDOW, MAX_BLOCK, MAX_SHIFT = 8, 64, 32768, 40
 BLOCK, WINDOW, LOAD_SHIFT = 4096, 8, 10
@@ -51,100 +51,47 @@ def make_cfg(M, block=BLOCK, window=WINDOW, load_shift=LOAD_SHIFT, constraint=No
     return NullCfg(antennas=M, block=int(block), window=int(window), load_shift=int(load_shift), c=(ctypes.c_double * 16)(*c))
 
 
-def out_end(block, window, in_end):
-    """the end of the outputs that recordings known up to input sample in_end - 1 support: all of them once W whole blocks are there"""
-    return in_end if in_end >= int(window) * int(block) else 0
-
-
-def first_needed(block, window, out):
-    """the first input sample that output `out` needs"""
-    return max(out // int(block) - int(window), 0) * int(block)
-
-
-def owned_blocks(block, out_first, n_out):
-    """blocks that begin in out_first .. out_first + n_out - 1"""
-    block = int(block)
-    return max(0, -(-(out_first + n_out) // block) - -(-out_first // block)) if n_out > 0 else 0
-
-
 def _device_int8(engine, data):
-    torch = nat.require_torch()
-    if torch.is_tensor(data):
-        if not data.is_cuda or data.dim() != 1 or data.dtype not in (torch.uint8, torch.int8):
-            raise ValueError("an antenna's data must be a flat int8 or uint8 CUDA tensor or a bytes-like object")
-        return (data if data.is_contiguous() else data.contiguous()).view(torch.int8)
-    h = np.frombuffer(data, dtype=np.int8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).reshape(-1).view(np.int8)
-    return torch.from_numpy(np.array(h, copy=True)).to("cuda:%d" % engine.device)
+    return streaming.device_flat(engine, data, ("uint8", "int8"), "an antenna's data must be a flat int8 or uint8 CUDA tensor or a bytes-like object", "int8")
 
 
-class Nuller:
+class Nuller(streaming.Handle):
     """The open device side of one configuration (gacq_null_open); run() is asynchronous on torch's current stream.  stats() reads what
     the runs so far have counted.  Closed with its engine at the latest."""
+    _close, _what = "gacq_null_close", "nuller"
 
     def __init__(self, engine, M, block=BLOCK, window=WINDOW, load_shift=LOAD_SHIFT, constraint=None):
-        torch = nat.require_torch()
         self.engine, self.M, self.block, self.window, self.load_shift = engine, int(M), int(block), int(window), int(load_shift)
         self.cfg = make_cfg(self.M, block, window, load_shift, constraint)
-        self._h = None
-        h = ctypes.c_void_p()
-        nat.check(nat.lib.gacq_null_open(engine._ctx, ctypes.addressof(self.cfg), ctypes.byref(h)), engine._ctx)
-        self._h = h
-        self._stats = torch.zeros(2, dtype=torch.int64, device="cuda:%d" % engine.device)
-        engine._live.add(self)                      # Engine.close() closes what lives on its context
+        self._open(engine, nat.lib.gacq_null_open, ctypes.addressof(self.cfg), stats=True)
 
     def run(self, d_inputs, in_first, out_first, n_out, gain, dtype="int8", weights=False, cov=False):
         """outputs out_first .. out_first + n_out - 1 of the recordings whose samples in_first .. are the int8 pairs of the M flat int8
         CUDA tensors d_inputs (two entries may be one tensor): a flat int8 tensor [2 n_out] or complex64 [n_out]; with weights also the
         int32 weights [owned blocks][M][2] of the blocks that begin in the range, with cov their int64 window sums [blocks][M][M][2]"""
         torch = nat.require_torch()
-        if dtype not in ("int8", "complex64"):
-            raise ValueError("dtype must be 'int8' or 'complex64', not %r" % (dtype,))
-        if not self._h:
-            raise ValueError("the nuller is closed")
+        self._check_open()
         d_inputs = list(d_inputs)
         if len(d_inputs) != self.M:
             raise ValueError("%d antennas take %d inputs" % (self.M, self.M))
-        cplx = dtype == "complex64"
         n_out, out_first = int(n_out), int(out_first)
         dev = d_inputs[0].device
-        out = torch.empty(max(n_out, 0) * (1 if cplx else 2), dtype=torch.complex64 if cplx else torch.int8, device=dev)
+        cplx, out = streaming.iq_out(n_out, dtype, dev)
         nblk = owned_blocks(self.block, out_first, n_out)
         wq = torch.empty((nblk, self.M, 2), dtype=torch.int32, device=dev) if weights else None
         cv = torch.empty((nblk, self.M, self.M, 2), dtype=torch.int64, device=dev) if cov else None
         count = min(d.numel() for d in d_inputs) // 2
-        if count or n_out:
-            self.engine.use_torch_stream(dev)
-            # a tensor without elements has no address to speak of: the call still makes its checks
-            some = next((d.data_ptr() for d in d_inputs if d.numel()), 0)
-            ptrs = (ctypes.c_void_p * self.M)(*[d.data_ptr() if d.numel() else some for d in d_inputs])
+
+        def call(src, dst):
+            ptrs = (ctypes.c_void_p * self.M)(*src)
             nat.check(nat.lib.gacq_null_run_dev(self._h, ctypes.cast(ptrs, ctypes.c_void_p), int(in_first), count, out_first, n_out, float(gain), int(cplx),
-                                                ctypes.c_void_p(out.data_ptr() if out.numel() else some), ctypes.c_void_p(self._stats.data_ptr()),
+                                                ctypes.c_void_p(dst), ctypes.c_void_p(self._stats.data_ptr()),
                                                 ctypes.c_void_p(wq.data_ptr()) if weights and nblk else None,
                                                 ctypes.c_void_p(cv.data_ptr()) if cov and nblk else None), self.engine._ctx)
+
+        streaming.launch(self.engine, d_inputs, count, out, n_out, call)
         res = (out,) + ((wq,) if weights else ()) + ((cv,) if cov else ())
         return res if len(res) > 1 else out
-
-    def stats(self):
-        """(components the clip changed, blocks) over the runs so far"""
-        c, b = self._stats.cpu().tolist()
-        return int(c), int(b)
-
-    def close(self):
-        if self._h:
-            nat.lib.gacq_null_close(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def convert(engine, xs, block=BLOCK, window=WINDOW, load_shift=LOAD_SHIFT, constraint=None, gain=1.0, dtype="int8", weights=False):
@@ -174,7 +121,7 @@ def auto_gain(engine, firsts, block=BLOCK, window=WINDOW, load_shift=LOAD_SHIFT,
         return ingest.rms_gain(nl.run(ds, 0, 0, p, 1.0, "complex64").cpu().numpy(), target_rms)
 
 
-class Stream:
+class Stream(streaming.Chunks):
     """Recordings fed piece by piece: feed(pieces) takes one piece per antenna (of equal length) and returns the outputs the pieces
     complete; the concatenation of what the calls return is what one convert() of the whole recordings gives, and so are stats() and
     the weights.  The W blocks under the next output's weights stay on the device."""
@@ -182,30 +129,23 @@ class Stream:
     def __init__(self, engine, M, gain, block=BLOCK, window=WINDOW, load_shift=LOAD_SHIFT, constraint=None, dtype="int8", weights=False):
         self.nl = Nuller(engine, M, block, window, load_shift, constraint)
         self.engine, self.gain, self.dtype, self.weights = engine, float(gain), dtype, bool(weights)
-        self.in_first = 0            # absolute index of the first input sample of the kept tails
-        self.next_out = 0            # the next output sample
-        self._tails = None
         self.traces = []             # weights: the weights, call by call
-
-    def feed(self, pieces):
-        torch = nat.require_torch()
         nl = self.nl
-        ds = [_device_int8(self.engine, p) for p in pieces]
-        if len(ds) != nl.M or len(set(d.numel() for d in ds)) != 1 or ds[0].numel() % 2:
-            raise ValueError("one piece per antenna, all of one length, in whole samples")
-        if self._tails is not None and self._tails[0].numel():
-            ds = [torch.cat([t, d]) for t, d in zip(self._tails, ds)]
-        in_count = ds[0].numel() // 2
-        n_out = max(0, out_end(nl.block, nl.window, self.in_first + in_count) - self.next_out)
-        got = nl.run(ds, self.in_first, self.next_out, n_out, self.gain, self.dtype, weights=self.weights)
+        super().__init__(16, lambda in_first, in_count: out_end(nl.block, nl.window, in_first + in_count), self._run,
+                         lambda out: first_needed(nl.block, nl.window, out))
+
+    def _run(self, ds, in_first, in_count, out_first, n_out, k):
+        got = self.nl.run(ds, in_first, out_first, n_out, self.gain, self.dtype, weights=self.weights)
         if self.weights:
             got, w = got
             self.traces.append(w)
-        self.next_out += n_out
-        keep = max(self.in_first, first_needed(nl.block, nl.window, self.next_out))
-        self._tails = [d[2 * (keep - self.in_first):].clone() for d in ds]
-        self.in_first = keep
         return got
+
+    def feed(self, pieces):
+        ds = [_device_int8(self.engine, p) for p in pieces]
+        if len(ds) != self.nl.M or len(set(d.numel() for d in ds)) != 1 or ds[0].numel() % 2:
+            raise ValueError("one piece per antenna, all of one length, in whole samples")
+        return self.feed_all(ds)
 
     def stats(self):
         return self.nl.stats()
@@ -233,46 +173,35 @@ def convert_files(engine, fins, fout, block=BLOCK, window=WINDOW, load_shift=LOA
     gain, that of the first 65536 outputs whatever the piece size (shorter pieces are read ahead until they hold its window).
     (gain, samples written, clipped components)."""
     M = len(fins)
-    st, n = None, 0
+    st = None
     window_in = 0 if gain is not None else auto_window(block, window)
-    held = []                                       # automatic gain: the pieces read until they hold the window (or the files end)
 
     def feed(ps):
-        nonlocal n
         out = st.feed(ps)
-        n += out.numel() // (2 if dtype == "int8" else 1)
-        fout.write(out.cpu().numpy().tobytes())
         w = st.traces.pop()
         if ftrace is not None and w.numel():
             ftrace.write(w.cpu().numpy().tobytes())
+        return [out]
 
-    def start():
+    def start(held):
         nonlocal st, gain
         if gain is None and not held:
             gain = 1.0
         if gain is None:
-            firsts =[np.concatenate([h[p] for h in held])[:2 * window_in] for p in range(M)]
+            firsts = [np.concatenate([h[p] for h in held])[:2 * window_in] for p in range(M)]
             gain = auto_gain(engine, firsts, block, window, load_shift, constraint, target_rms) if out_end(block, window, len(firsts[0]) // 2) else 1.0
         st = Stream(engine, M, gain, block, window, load_shift, constraint, dtype, weights=True)
-        for ps in held:
-            feed(ps)
-        held.clear()
+        return feed
 
     try:
-        for ps in lockstep(fins, piece_bytes):
-            if st is None:
-                held.append(ps)
-                if sum(len(h[0]) for h in held) >= 2 * window_in:
-                    start()
-            else:
-                feed(ps)
-        if st is None:
-            start()
+        n = streaming.pump(lockstep(fins, piece_bytes), start, [fout], 2 if dtype == "int8" else 1, 2 * window_in, lambda ps: len(ps[0]))
+        if n is None:
+            start([])
         clipped = st.stats()[0]
     finally:
         if st is not None:
             st.close()
-    return gain, n, clipped
+    return gain, n[0] if n else 0, clipped
 
 
 def _complex(text):
@@ -313,7 +242,7 @@ def parse(argv):
         if len(z) != M or not np.all(np.isfinite(z.view(np.float64))) or not np.any(z != 0):
             raise SystemExit("nulling: --constraint takes %d finite entries RE,IM, not all zero" % M)
     for v in (a.gain, a.target_rms):
-        if v is not None and not (v > 0.0 and math.isfinite(v) and math.isfinite(float(np.float32(v))) and float(np.float32(v)) > 0.0):
+        if v is not None and not streaming.positive_finite_fp32(v):
             raise SystemExit("nulling: need a positive, finite --gain / --target-rms")
     return a
 
@@ -324,37 +253,16 @@ def report_line(M, block, window, gain, clipped, samples):
 
 def run(argv, out=None, piece_bytes=rawfile.PIECE_BYTES):
     a = parse(argv)
-    to_stdout = a.out == "-"
-    if out is None:
-        out = sys.stderr if to_stdout else sys.stdout
-    fins = [open(name, "rb") for name in a.inputs]
-    fout = sys.stdout.buffer if to_stdout else open(a.out, "wb")
-    ftrace = open(a.weights_trace, "wb") if a.weights_trace else None
-    eng = acquire.Engine(a.device)
-    try:
-        gain, n, clipped = convert_files(eng, fins, fout, a.block, a.window, a.load_shift, a.constraint, a.gain, a.target_rms,
-                                         "complex64" if a.complex64 else "int8", ftrace, piece_bytes)
-        fout.flush()
-    finally:
-        eng.close()
-        for f in fins:
-            f.close()
-        if not to_stdout:
-            fout.close()
-        if ftrace is not None:
-            ftrace.close()
-    line = report_line(len(fins), a.block, a.window, gain, clipped, n)
-    print(line, file=out)
+    with streaming.shell(a.device, a.inputs, [a.out], a.weights_trace, out, stdin=False) as sh:
+        gain, n, clipped = convert_files(sh.engine, sh.fins, sh.fouts[0], a.block, a.window, a.load_shift, a.constraint, a.gain, a.target_rms,
+                                         "complex64" if a.complex64 else "int8", sh.ftrace, piece_bytes)
+    line = report_line(len(a.inputs), a.block, a.window, gain, clipped, n)
+    print(line, file=sh.report)
     return line
 
 
 def main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
-    if not argv or argv[0] in ("-h", "--help"):
-        print(__doc__)
-        return 0
-    run(argv)
-    return 0
+    return streaming.main(argv, __doc__, run)
 
 
 if __name__ == "__main__":

@@ -20,14 +20,14 @@ up to three trailing samples are dropped.  A recording shorter than W blocks giv
 tests/requant_oracle.py restates it in numpy."""
 import argparse
 import ctypes
-import math
 import sys
 from fractions import Fraction
 
 import numpy as np
 
 from . import _native as nat
-from . import acquire, ingest, rawfile
+from . import ingest, rawfile, streaming
+from .streaming import first_needed                           # first_needed(block, window, out), part of this module as before
 
 S8, U8, S16, F32, PACKED = ingest.S8, ingest.U8, ingest.S16, ingest.F32, ingest.PACKED
 NAMES = ingest.NAMES
@@ -49,7 +49,7 @@ def tables(target_rms, block, window, step=STEP, K=GAINS, g_max=G_MAX):
     the float32 gains and the double target (Fractions), capped at 2^64 - 1, which no level reaches; the library takes both tables as
     they are."""
     target_rms, K, step = float(target_rms), int(K), int(step)
-    if not (target_rms > 0.0 and math.isfinite(target_rms)) or not 1 <= K <= MAX_GAINS or step < 1 or not (g_max > 0.0 and math.isfinite(g_max)):
+    if not streaming.positive_finite(target_rms) or not 1 <= K <= MAX_GAINS or step < 1 or not streaming.positive_finite(g_max):
         raise ValueError("tables: need a positive, finite target rms and g_max, 1..%d gains, a step of at least 1" % MAX_GAINS)
     G = np.array([g_max * 2.0 ** (-k / step) for k in range(K)], dtype=np.float32)
     if not (np.all(np.isfinite(G)) and np.all(G > 0)):
@@ -109,33 +109,20 @@ def make_cfg(fmt, block, window, ngains, in_bits=8):
 def out_end(fmt, block, window, in_end):
     """the end of the outputs that a recording known up to input sample in_end - 1 supports: all of it once W whole blocks are there,
     in whole output bytes"""
-    if in_end < int(window) * int(block):
-        return 0
-    return in_end // fmt.unit * fmt.unit
-
-
-def first_needed(block, window, out):
-    """the first input sample that output `out` needs"""
-    return max(out // int(block) - int(window), 0) * int(block)
+    return streaming.out_end(block, window, in_end, fmt.unit)
 
 
 def _device_bytes(engine, data):
-    torch = nat.require_torch()
-    if torch.is_tensor(data):
-        if not data.is_cuda or data.dim() != 1 or data.dtype not in (torch.uint8, torch.int8, torch.int16):
-            raise ValueError("data must be a flat int8, uint8 or int16 CUDA tensor or a bytes-like object")
-        data = data if data.is_contiguous() else data.contiguous()
-        return data.view(torch.uint8)
-    h = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
-    return torch.from_numpy(np.array(h, copy=True)).to("cuda:%d" % engine.device)
+    return streaming.device_flat(engine, data, ("uint8", "int8", "int16"), "data must be a flat int8, uint8 or int16 CUDA tensor or a bytes-like object",
+                                 "uint8")
 
 
-class Requantizer:
+class Requantizer(streaming.Handle):
     """The open device side of one configuration (gacq_requant_open: the tables are uploaded once); run() is asynchronous on torch's
     current stream.  stats() reads what the runs so far have counted.  Closed with its engine at the latest."""
+    _close, _what = "gacq_requant_close", "requantizer"
 
     def __init__(self, engine, fmt, gains, thresholds, block=BLOCK, window=WINDOW, in_bits=8):
-        torch = nat.require_torch()
         self.engine, self.fmt, self.block, self.window, self.in_bits = engine, as_format(fmt), int(block), int(window), int(in_bits)
         self.gains = np.ascontiguousarray(gains, dtype=np.float32).reshape(-1)
         self.thresholds = np.ascontiguousarray(thresholds, dtype=np.uint64).reshape(-1)
@@ -143,58 +130,26 @@ class Requantizer:
             raise ValueError("K gains take K - 1 thresholds")
         self.cfg = make_cfg(self.fmt, self.block, self.window, len(self.gains), self.in_bits)
         self.in_bytes = 2 * self.in_bits // 8                               # per input sample
-        self._h = None
         thr = self.thresholds if len(self.thresholds) else np.zeros(1, dtype=np.uint64)
-        h = ctypes.c_void_p()
-        nat.check(nat.lib.gacq_requant_open(engine._ctx, ctypes.addressof(self.cfg), ctypes.c_void_p(self.gains.ctypes.data), ctypes.c_void_p(thr.ctypes.data),
-                                            ctypes.byref(h)), engine._ctx)
-        self._h = h
-        self._stats = torch.zeros(2, dtype=torch.int64, device="cuda:%d" % engine.device)
-        engine._live.add(self)                      # Engine.close() closes what lives on its context
+        self._open(engine, nat.lib.gacq_requant_open, ctypes.addressof(self.cfg), ctypes.c_void_p(self.gains.ctypes.data), ctypes.c_void_p(thr.ctypes.data),
+                   stats=True)
 
     def run(self, d, in_first, out_first, n_out, trace=False):
         """outputs out_first .. out_first + n_out - 1 of the recording whose samples in_first .. are the bytes of the flat uint8 CUDA
         tensor d: a flat tensor of the format's type (int8 / uint8 / int16 pairs, complex64, bytes of packed codes); with trace also
         the uint8 gain indices of the blocks that begin in the range"""
         torch = nat.require_torch()
-        if not self._h:
-            raise ValueError("the requantizer is closed")
+        self._check_open()
         n_out, out_first = int(n_out), int(out_first)
-        nbytes = self.fmt.nbytes(max(n_out, 0))
-        out = torch.empty(nbytes, dtype=torch.uint8, device=d.device)
-        nblk = max(0, -(-(out_first + n_out) // self.block) - -(-out_first // self.block)) if n_out > 0 else 0
+        out = torch.empty(self.fmt.nbytes(max(n_out, 0)), dtype=torch.uint8, device=d.device)
+        nblk = streaming.owned_blocks(self.block, out_first, n_out)
         kidx = torch.empty(nblk, dtype=torch.uint8, device=d.device) if trace else None
-        if d.numel() or n_out:
-            self.engine.use_torch_stream(d.device)
-            # an output without elements has no address to speak of: the call still makes its checks
-            nat.check(nat.lib.gacq_requant_run_dev(self._h, ctypes.c_void_p(d.data_ptr() if d.numel() else 0), int(in_first), d.numel() // self.in_bytes,
-                                                   out_first, n_out, ctypes.c_void_p(out.data_ptr() if nbytes else d.data_ptr()),
-                                                   ctypes.c_void_p(self._stats.data_ptr()), ctypes.c_void_p(kidx.data_ptr()) if trace and nblk else None),
-                      self.engine._ctx)
+        streaming.launch(self.engine, [d], d.numel(), out, n_out, lambda src, dst: nat.check(
+            nat.lib.gacq_requant_run_dev(self._h, ctypes.c_void_p(src[0]), int(in_first), d.numel() // self.in_bytes, out_first, n_out, ctypes.c_void_p(dst),
+                                         ctypes.c_void_p(self._stats.data_ptr()), ctypes.c_void_p(kidx.data_ptr()) if trace and nblk else None),
+            self.engine._ctx))
         out = out.view(self.fmt.torch_dtype(torch))
         return (out, kidx) if trace else out
-
-    def stats(self):
-        """(components the clip changed, blocks) over the runs so far"""
-        c, b = self._stats.cpu().tolist()
-        return int(c), int(b)
-
-    def close(self):
-        if self._h:
-            nat.lib.gacq_requant_close(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def convert(engine, fmt, data, gains, thresholds, block=BLOCK, window=WINDOW, in_bits=8, trace=False):
@@ -209,7 +164,7 @@ def convert(engine, fmt, data, gains, thresholds, block=BLOCK, window=WINDOW, in
     return (got[0], st, got[1]) if trace else (got, st)
 
 
-class Stream:
+class Stream(streaming.Chunks):
     """A recording fed chunk by chunk: feed(chunk) returns the outputs the chunk completes, and the concatenation of what the calls
     return is what one convert() of the whole recording gives; so are stats() and, with trace, the gain indices.  What the next
     outputs still need stays on the device: the W blocks under the next output's level, the samples of an output byte that the chunk
@@ -218,29 +173,20 @@ class Stream:
     def __init__(self, engine, fmt, gains, thresholds, block=BLOCK, window=WINDOW, in_bits=8, trace=False):
         self.rq = Requantizer(engine, fmt, gains, thresholds, block, window, in_bits)
         self.engine, self.fmt, self.trace = engine, self.rq.fmt, bool(trace)
-        self.in_first = 0            # absolute index of the first input sample of the kept tail
-        self.next_out = 0            # the next output sample
-        self._tail = None
         self.indices = []            # trace: the gain indices, call by call
+        rq = self.rq
+        super().__init__(8 * rq.in_bytes, lambda in_first, in_count: out_end(self.fmt, rq.block, rq.window, in_first + in_count), self._run,
+                         lambda out: first_needed(rq.block, rq.window, out))
+
+    def _run(self, ds, in_first, in_count, out_first, n_out, k):
+        got = self.rq.run(ds[0], in_first, out_first, n_out, self.trace)
+        if self.trace:
+            got, kidx = got
+            self.indices.append(kidx)
+        return got
 
     def feed(self, chunk):
-        torch = nat.require_torch()
-        rq = self.rq
-        d = _device_bytes(self.engine, chunk)
-        if self._tail is not None and self._tail.numel():
-            d = torch.cat([self._tail, d])
-        in_count = d.numel() // rq.in_bytes
-        end = out_end(self.fmt, rq.block, rq.window, self.in_first + in_count)
-        n_out = max(0, end - self.next_out)
-        got = rq.run(d[:in_count * rq.in_bytes], self.in_first, self.next_out, n_out, self.trace)
-        if self.trace:
-            got, k = got
-            self.indices.append(k)
-        self.next_out += n_out
-        keep = max(self.in_first, first_needed(rq.block, rq.window, self.next_out))
-        self._tail = d[(keep - self.in_first) * rq.in_bytes:].clone()
-        self.in_first = keep
-        return got
+        return self.feed_all([_device_bytes(self.engine, chunk)])
 
     def stats(self):
         return self.rq.stats()
@@ -254,17 +200,21 @@ def convert_file(engine, fmt, fin, fout, gains, thresholds, block=BLOCK, window=
     used; None, None without output)."""
     st = Stream(engine, fmt, gains, thresholds, block, window, in_bits, trace=True)
     n, lo, hi = 0, None, None
+
+    def feed(piece):
+        nonlocal n, lo, hi
+        out = st.feed(piece)
+        n += out.numel() * out.element_size() * 8 // st.fmt.sample_bits
+        k = st.indices.pop().cpu().numpy()
+        if len(k):
+            lo = int(k.min()) if lo is None else min(lo, int(k.min()))
+            hi = int(k.max()) if hi is None else max(hi, int(k.max()))
+            if ftrace is not None:
+                ftrace.write(k.tobytes())
+        return [out]
+
     try:
-        for piece in rawfile.read_pieces(fin, 2 * in_bits // 8, piece_bytes):
-            out = st.feed(piece.view(np.uint8))
-            n += out.numel() * out.element_size() * 8 // st.fmt.sample_bits
-            fout.write(out.cpu().numpy().tobytes())
-            k = st.indices.pop().cpu().numpy()
-            if len(k):
-                lo = int(k.min()) if lo is None else min(lo, int(k.min()))
-                hi = int(k.max()) if hi is None else max(hi, int(k.max()))
-                if ftrace is not None:
-                    ftrace.write(k.tobytes())
+        streaming.pump(rawfile.read_pieces(fin, 2 * in_bits // 8, piece_bytes), lambda held: feed, [fout], 1)
         clipped = st.stats()[0]
     finally:
         st.close()
@@ -298,7 +248,7 @@ def parse(argv):
     if a.block < 16 or a.block > MAX_BLOCK or a.block % 16 or not 1 <= a.window <= MAX_WINDOW:
         raise SystemExit("requant: --block is a multiple of 16 in 16..%d and --window lies in 1..%d" % (MAX_BLOCK, MAX_WINDOW))
     for v in (a.gain, a.target_rms):
-        if v is not None and not (v > 0.0 and math.isfinite(v) and math.isfinite(float(np.float32(v))) and float(np.float32(v)) > 0.0):
+        if v is not None and not streaming.positive_finite_fp32(v):
             raise SystemExit("requant: need a positive, finite --gain / --target-rms")
     if a.gain is not None:
         G, T = fixed(a.gain)
@@ -315,37 +265,17 @@ def report_lines(fmt, block, window, G, lo, hi, clipped, samples):
 
 def run(argv, out=None, piece_bytes=rawfile.PIECE_BYTES):
     a, fmt, G, T = parse(argv)
-    to_stdout = a.output_filename == "-"
-    if out is None:
-        out = sys.stderr if to_stdout else sys.stdout
-    fin = sys.stdin.buffer if a.input_filename == "-" else open(a.input_filename, "rb")
-    fout = sys.stdout.buffer if to_stdout else open(a.output_filename, "wb")
-    ftrace = open(a.trace, "wb") if a.trace else None
-    eng = acquire.Engine(a.device)
-    try:
-        n, clipped, lo, hi = convert_file(eng, fmt, fin, fout, G, T, a.block, a.window, 16 if a.in_format == "s16" else 8, ftrace, piece_bytes)
-        fout.flush()
-    finally:
-        eng.close()
-        if fin is not sys.stdin.buffer:
-            fin.close()
-        if not to_stdout:
-            fout.close()
-        if ftrace is not None:
-            ftrace.close()
+    with streaming.shell(a.device, [a.input_filename], [a.output_filename], a.trace, out) as sh:
+        n, clipped, lo, hi = convert_file(sh.engine, fmt, sh.fins[0], sh.fouts[0], G, T, a.block, a.window, 16 if a.in_format == "s16" else 8, sh.ftrace,
+                                          piece_bytes)
     lines = report_lines(fmt, a.block, a.window, G, lo, hi, clipped, n)
     for line in lines:
-        print(line, file=out)
+        print(line, file=sh.report)
     return lines
 
 
 def main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
-    if not argv or argv[0] in ("-h", "--help"):
-        print(__doc__)
-        return 0
-    run(argv)
-    return 0
+    return streaming.main(argv, __doc__, run)
 
 
 if __name__ == "__main__":

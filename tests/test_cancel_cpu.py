@@ -144,6 +144,7 @@ def test_cancel_check_refuses_every_bad_argument_and_accepts_the_unchanged_call(
         rc = raw_check(**change)
         assert rc == code, (label, rc, nat.lib.gacq_last_error(None))
         assert nat.lib.gacq_last_error(None)
+        assert nat.lib.gacq_last_error(None).startswith(b"gacq_cancel: "), label   # every message names its own tool
     assert raw_check() == 0
     assert raw_check(n_out=0, in_count=0) == 0                                       # n_out = 0 does nothing
     # without estimate a segment may reach past the input: only the output samples are needed

@@ -145,6 +145,7 @@ def bad_run_calls():
 def test_every_refusal_through_gacq_ddc_check_without_a_device():
     for label, code, change in bad_config_calls() + bad_run_calls():
         assert raw_check(**change) == code, (label, nat.lib.gacq_last_error(None))
+        assert nat.lib.gacq_last_error(None).startswith(b"gacq_ddc: "), label       # every message names its own tool
     assert raw_check() == 0 and raw_check(in_count=99 * 4 + 17) == 0 and raw_check(n_out=0, in_count=0) == 0
     assert raw_check(in_first=24, in_count=976, out_first=10, n_out=50) == 0
     good = np.zeros(33, dtype=np.int64)

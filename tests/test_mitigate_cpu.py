@@ -150,6 +150,7 @@ def bad_calls():
 def test_every_refusal_through_the_raw_abi_without_a_context():
     for label, code, change in bad_calls():
         assert raw_check(**change) == code, (label, nat.lib.gacq_last_error(None))
+        assert nat.lib.gacq_last_error(None).startswith(b"gacq_mitigate_dev: "), label      # every message names its own tool
     assert raw_check() == 0 and raw_check(in_count=5 * 32 + 2) == 0 and raw_check(n_out=0, in_count=0) == 0
     assert raw_check(out_first=64, in_first=32 - 2, in_count=900) == 0
     assert raw_check(nfft=0, blank=5.0, in_count=102) == 0

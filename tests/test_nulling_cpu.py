@@ -97,6 +97,7 @@ def test_gacq_null_check_refuses_through_the_raw_abi():
     for bad in (dict(M=1), dict(M=9), dict(block=0), dict(block=32), dict(block=96), dict(block=65536), dict(block=32768 + 64), dict(window=0),
                 dict(window=65), dict(load_shift=-1), dict(load_shift=41)):
         assert _check(_cfg(**bad)) == BAD_ARG, bad
+        assert nat.lib.gacq_last_error(None).startswith(b"gacq_null: "), bad                    # every message names its own tool
         assert nat.lib.gacq_null_tile(ctypes.addressof(_cfg(**bad))) == BAD_ARG, bad
     for ok in (dict(M=2), dict(M=8), dict(block=64), dict(block=32768), dict(window=1), dict(window=64, block=64), dict(load_shift=0), dict(load_shift=40)):
         assert _check(_cfg(**ok)) == 0, ok
@@ -109,12 +110,12 @@ def test_gacq_null_check_refuses_through_the_raw_abi():
     assert _check(c) == 0
     # the gain: finite and positive, as a double and as a float
     for g in (0.0, -1.0, float("nan"), float("inf"), 1e-50, 1e39):
-        assert _check(_cfg(), gain=g) == BAD_ARG, g
+        assert _check(_cfg(), gain=g) == BAD_ARG and nat.lib.gacq_last_error(None).startswith(b"gacq_null: the gain"), g
     # indices and counts
     big = (1 << 48) + 1
     for kw in (dict(in_first=-1), dict(in_count=-1), dict(out_first=-1), dict(n_out=-1), dict(in_first=big), dict(in_count=big), dict(out_first=big),
                dict(n_out=big)):
-        assert _check(_cfg(), **kw) == BAD_ARG, kw
+        assert _check(_cfg(), **kw) == BAD_ARG and nat.lib.gacq_last_error(None).startswith(b"gacq_null: need 0 <="), kw
     assert b"2^48" in nat.lib.gacq_last_error(None)
     # ranges: output j in block b needs j and max(b - W, 0) Lb .. max(b, W) Lb - 1
     c = _cfg(block=64, window=3)
@@ -123,7 +124,7 @@ def test_gacq_null_check_refuses_through_the_raw_abi():
     assert _check(c, 64, 1000, 256, 10) == 0 and _check(c, 65, 1000, 256, 10) == SHORT_INPUT    # block 4 needs blocks 1 .. 3
     assert _check(c, 64, 1000, 255, 10) == SHORT_INPUT                                          # block 3 needs block 0
     assert _check(c, 64, 202, 256, 10) == 0 and _check(c, 64, 201, 256, 10) == SHORT_INPUT
-    assert b"need input samples" in nat.lib.gacq_last_error(None)
+    assert b"need input samples" in nat.lib.gacq_last_error(None) and nat.lib.gacq_last_error(None).startswith(b"gacq_null: outputs 256 .. 265 ")
     assert _check(c, 5, 0, 7, 0) == 0                                                           # n_out = 0 needs nothing
 
 

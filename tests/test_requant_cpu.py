@@ -210,6 +210,7 @@ def bad_run_calls():
 def test_every_refusal_through_gacq_requant_check_without_a_device():
     for label, code, change in bad_config_calls() + bad_run_calls():
         assert raw_check(**change) == code, (label, nat.lib.gacq_last_error(None))
+        assert nat.lib.gacq_last_error(None).startswith(b"gacq_requant: "), label   # every message names its own tool
     assert b"need input samples" in nat.lib.gacq_last_error(None)
     assert raw_check() == 0 and raw_check(n_out=0, in_count=0) == 0 and raw_check(in_count=192, n_out=192) == 0 and raw_check(in_count=193, n_out=193) == 0
     assert raw_check(in_first=256, in_count=744, out_first=448, n_out=552) == 0                 # block 7 needs blocks 4 .. 6
