@@ -108,6 +108,11 @@ def needed(Lb, W, out_first, n_out):
     return max(b_lo - W, 0) * Lb, max(out_first + n_out, W * Lb)
 
 
+def supported(Lb, W, in_first, in_count):
+    """the end of the outputs that input samples in_first .. in_first + in_count - 1 support: all of them once W whole blocks are there"""
+    return in_first + in_count if in_first + in_count >= W * Lb else 0
+
+
 def run(xs, in_first, out_first, n_out, Lb, W, load_shift=10, c=None, gain=1.0, complex64=False):
     """Outputs out_first .. out_first + n_out - 1 from arrays that hold the antennas' samples from in_first on.  A dict: out (int8
     interleaved or complex64), clipped, owned, wq [owned block][M][2] int32, cov [owned block][M][M][2] int64, margin, and wq_all /

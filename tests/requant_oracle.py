@@ -34,14 +34,18 @@ def block_powers(c, x):
     return P
 
 
-def levels(c, P, nblocks):
-    """S(b), b < nblocks, as Python integers behind a uint64 array: the W powers before b, or the first W during the warm-up"""
+def levels(c, P, nblocks, first=0, p_first=0):
+    """S(b), first <= b < nblocks, as Python integers behind a uint64 array: the W powers before b, or the first W during the warm-up
+    (blocks below W).  P[i] is the power of block p_first + i: every block a level sums over must be among them."""
     W = c["window"]
-    assert len(P) >= W and nblocks <= len(P) + 1
     cum = [0]
     for p in P.tolist():                                     # Python integers: no width to think about
         cum.append(cum[-1] + p)
-    S = [cum[W] if b < W else cum[b] - cum[b - W] for b in range(nblocks)]
+    S = []
+    for b in range(first, nblocks):
+        lo, hi = (0, W) if b < W else (b - W, b)
+        assert lo >= p_first and hi - p_first <= len(P), "a block that the level of block %d sums over is not present" % b
+        S.append(cum[hi - p_first] - cum[lo - p_first])
     assert all(s <= 1 << 53 for s in S)
     return np.array(S, dtype=np.uint64)
 
@@ -63,25 +67,39 @@ def out_count(c, n_samples):
     return n_samples // unit(c) * unit(c)
 
 
-def evaluate(c, G, T, x, out_first=0, n_out=None):
-    """What gacq_requant_run_dev writes for outputs out_first .. out_first + n_out - 1 of the recording x (interleaved integers from
-    sample 0): (bytes as uint8, clipped components, owned blocks, k(b) of the owned blocks as uint8)."""
-    v = np.asarray(x).reshape(-1)
-    n = len(v) // 2
+def needed(c, out_first, n_out):
+    """(first, end) of the input samples that outputs out_first .. out_first + n_out - 1 need: output j of block b needs j itself and
+    blocks max(b - W, 0) .. max(b, W) - 1 whole"""
     Lb, W = c["block"], c["window"]
-    total = out_count(c, n)
+    return max(out_first // Lb - W, 0) * Lb, max(out_first + n_out, W * Lb)
+
+
+def supported(c, in_first, in_count):
+    """the end of the outputs that input samples in_first .. in_first + in_count - 1 support"""
+    return out_count(c, in_first + in_count)
+
+
+def evaluate(c, G, T, x, out_first=0, n_out=None, in_first=0):
+    """What gacq_requant_run_dev writes for outputs out_first .. out_first + n_out - 1 of the recording whose samples in_first ..
+    are x (interleaved integers; in_first, the absolute index of x[0], is a multiple of the block): (bytes as uint8, clipped
+    components, owned blocks, k(b) of the owned blocks as uint8).  Blocks are j div Lb of the absolute index j, and the warm-up applies
+    to the blocks below W only."""
+    v = np.asarray(x).reshape(-1)
+    Lb, W = c["block"], c["window"]
+    assert in_first >= 0 and in_first % Lb == 0
+    total = out_count(c, in_first + len(v) // 2)
     n_out = total - out_first if n_out is None else n_out
-    assert out_first >= 0 and n_out >= 0 and out_first + n_out <= total and out_first % unit(c) == 0 and n_out % unit(c) == 0
+    assert out_first >= in_first and n_out >= 0 and out_first + n_out <= total and out_first % unit(c) == 0 and n_out % unit(c) == 0
     G = np.asarray(G, dtype=np.float32)
     assert len(G) >= 1 and len(T) == len(G) - 1 and all(int(T[i]) <= int(T[i + 1]) for i in range(len(T) - 1))
     if n_out == 0:
         return np.zeros(0, dtype=np.uint8), 0, 0, np.zeros(0, dtype=np.uint8)
     P = block_powers(c, v)
-    nblocks = (out_first + n_out - 1) // Lb + 1
-    k = gain_indices(T, levels(c, P, nblocks))
+    b_lo, nblocks = out_first // Lb, (out_first + n_out - 1) // Lb + 1
+    k = gain_indices(T, levels(c, P, nblocks, b_lo, in_first // Lb))          # k[i] is that of block b_lo + i
     j = np.arange(out_first, out_first + n_out, dtype=np.int64)
-    g = np.repeat(G[k[j // Lb]], 2)                                           # per component
-    comp = v[2 * out_first:2 * (out_first + n_out)].astype(np.float32)        # exact: |component| <= 32768
+    g = np.repeat(G[k[j // Lb - b_lo]], 2)                                    # per component
+    comp = v[2 * (out_first - in_first):2 * (out_first - in_first + n_out)].astype(np.float32)        # exact: |component| <= 32768
     val = comp * g                                                            # one float32 multiply
     assert val.dtype == np.float32
     kind = c["container"]
@@ -108,7 +126,7 @@ def evaluate(c, G, T, x, out_first=0, n_out=None):
         shift = (8 - bits * (i + 1)) if c["msb_first"] else bits * i
         out = (codes.reshape(-1, per) << shift[None, :]).sum(axis=1).astype(np.uint8)
     first_owned = -(-out_first // Lb)
-    owned = k[first_owned:nblocks]
+    owned = k[first_owned - b_lo:]
     return np.ascontiguousarray(out), clipped, len(owned), owned.astype(np.uint8)
 
 

@@ -1,0 +1,236 @@
+"""CPU: what the device-side stream-contract tests (test_stream_contract_gpu.py) rest on, established without a device -- the case table
+covers the six tools and its drawn cuts and chunks have the properties the GPU tests count on; the new recordings satisfy the
+preconditions of the comparison rules they are held to (the nulling rounding-tie margin, the distance of the mitigate decisions from
+their thresholds); needed() and supported() of every adapter agree with each other; the far-end call of every configuration is the
+last one its tool's gacq_*_check accepts; and tests/requant_oracle.evaluate, which gained in_first, gives what it gave."""
+import numpy as np
+import pytest
+
+import nulling_cases
+import requant_cases
+import requant_oracle as RO
+import stream_contract_cases as S
+from gnss_dsp_tools_amd import _native as nat
+from gnss_dsp_tools_amd import ingest, streaming
+
+
+def test_the_table_covers_the_six_tools_and_their_configurations():
+    assert sorted(set(c.tool for c in S.CASES)) == sorted(S.TOOLS) and len(S.BY_NAME) == len(S.CASES)
+    names = set(S.BY_NAME)
+    assert {"ingest-2sm-real", "ingest-1ob-iq", "ingest-s16-iq", "mitigate-n128-blank", "mitigate-blank-only", "ddc-d5-t3", "requant-u8", "requant-2sm",
+            "cancel-two-sats", "nulling-m3-b128-w3", "nulling-m2-b192-w2"} == names
+    assert S.BY_NAME["ddc-d5-t3"].D % 2 == 1 and nulling_cases.TILE % 192 != 0
+
+
+@pytest.mark.parametrize("c", S.CASES, ids=S.case_id)
+def test_recordings_cuts_and_chunks_have_the_properties_the_gpu_tests_count_on(c):
+    rec = c.recording()
+    N = c.total()
+    assert len(rec) == c.inputs and len(set(len(r) for r in rec)) == 1 and all(r.dtype == np.uint8 for r in rec)
+    # one workgroup tile, a few blocks or runs and an odd remainder; nothing larger
+    assert c.tile + 2 * c.run_len < N <= c.tile + 6 * max(c.run_len, c.block_edge and getattr(c, "Lb", 64) or 0) + 64, (N, c.tile)
+    pts = c.cut_points()
+    assert c.tile in pts and c.tile - c.run_len in pts and c.tile + c.run_len in pts and len(pts) >= S.DRAWN_CUTS and pts == sorted(set(pts))
+    if c.block_edge is not None:
+        assert c.block_edge in pts and c.block_edge - c.run_len in pts and c.block_edge + c.run_len in pts
+    assert all(0 < p < N and p % c.unit == 0 for p in pts)
+    assert c.cut_points() == pts                                                       # seeded: the same list every time
+    # every piece's needed input lies in the recording and supports the piece, and one sample fewer at either end does not
+    for a, b in zip([0] + pts, pts + [N]):
+        lo, end = c.needed(a, b - a)
+        assert 0 <= lo <= c.first_needed(a) and end <= c.n_in() and (lo * c.in_bits) % 8 == 0
+        assert c.supported(lo, end - lo) >= b
+        assert c.supported(lo, end - lo - 1) < b
+        assert lo < c.low_short(a) and (c.low_short(a) * c.in_bits) % 8 == 0
+    sizes = c.chunk_sizes()
+    assert sum(sizes) == len(rec[0]) and len(sizes) <= S.MAX_CHUNKS and all(s % c.chunk_unit == 0 for s in sizes)
+    assert any(a == 0 and b == 0 for a, b in zip(sizes, sizes[1:]))                    # two empty chunks in a row
+    assert max(c.ends(0, c.samples(sizes[0]))) == 0                                    # the first chunk supports no output
+    assert all(s in [v * c.chunk_unit for v in S.CHUNK_SET] for s in sizes[:-1])
+    offs = c.offsets(len(pts) + 1)
+    assert offs.shape == (len(pts) + 1, c.inputs) and offs.min() >= 0 and offs.max() <= 15
+
+
+@pytest.mark.parametrize("c", S.CASES, ids=S.case_id)
+def test_the_near_call_lies_past_every_effect_of_sample_zero_and_its_shifts_straddle(c):
+    lo, o, n, cnt = c.near_call()
+    assert lo > 0 and c.first_needed(o) >= lo and n > c.tile and o + n <= c.total()
+    for k in (31, 32):
+        for what, s in c.straddles(k):
+            assert s % (c.shift_unit or 1) == 0 and ((lo + c.ratio * s) * c.in_bits) % 8 == 0
+            if what == "out":
+                assert o + s < 1 << k < o + s + n - 1
+            else:
+                assert lo + c.ratio * s < 1 << k < lo + c.ratio * s + cnt - 1
+    if c.tool in ("requant", "nulling"):
+        assert lo % c.Lb == 0 and o >= (c.W + 1) * c.Lb                                # in_first on a block, outputs past the warm-up
+
+
+@pytest.mark.parametrize("c", [c for c in S.CASES if c.check is not None], ids=S.case_id)
+def test_the_far_end_call_is_the_last_one_the_check_accepts(c):
+    """the limit is the check's: the test finds it by asking.  gacq_ingest_dev has no check entry of its own and refuses every call
+    without a context, so its three configurations are asked on the device (test_stream_contract_gpu.py)."""
+    o, s = c.far_end(c.accepts)
+    lo, o, n, cnt = c.near_call(o)
+    assert c.check(lo + c.ratio * s, cnt, o + s, n, s) == 0
+    assert c.check(lo + c.ratio * s + c.ratio, cnt, o + s + 1, n, s + 1) == S.BAD_ARG      # one sample further
+    print(c.name, "far end: outputs", o + s, "..", o + s + n - 1, "inputs from", lo + c.ratio * s, "-", nat.lib.gacq_last_error(None).decode())
+    assert max(lo + c.ratio * s + cnt, o + s + n) >= ingest.MAX_INDEX                  # the call really lies at the limit
+    assert n > c.tile and s % (c.shift_unit or 1) == 0
+
+
+def test_gacq_ingest_dev_without_a_context_refuses_the_far_call_too():
+    c = S.BY_NAME["ingest-s16-iq"]
+    assert c.check is None
+    lo, o, n, cnt = c.near_call()
+    buf = np.zeros(8 * cnt, dtype=np.uint8)
+    out = np.zeros(2 * n, dtype=np.int8)
+    fake = type("E", (), {"_ctx": None})()
+    assert c.raw(fake, None, [type("D", (), {"data_ptr": lambda self: buf.ctypes.data})()], lo, cnt, o, n, type("D", (), {"data_ptr": lambda self: out.ctypes.data})()) < 0
+    assert not out.any()
+
+
+def test_mitigate_decisions_of_the_new_recordings_keep_their_distance_from_the_thresholds():
+    """as test_mitigate_cpu holds its cases: margin >= 1e-4, the float32 evaluation takes the same decisions, a bound below 1e-4"""
+    c = S.BY_NAME["mitigate-n128-blank"]
+    for in_first, out_first, n_out in ((0, 0, c.total()), c.near_call()[:3]):
+        lo, end = c.needed(out_first, n_out)
+        assert lo == in_first
+        ref, bound, top, f32 = c.oracle(c.cut(lo, end), lo, out_first, n_out)
+        print(c.name, out_first, n_out, "margin %.3g, float32 deviation %.3g of max |y| = %.3g, blanked %d, bins %d" % (ref.margin, bound / 4.0, top, ref.blanked, ref.bins))
+        assert ref.margin >= 1e-4 and ref.bins > 0 and ref.blanked > 0 and 0 < bound < 1e-4
+        assert np.array_equal(f32.frame_bins, ref.frame_bins) and (f32.blanked, f32.frames, f32.bins) == (ref.blanked, ref.frames, ref.bins)
+    b = S.BY_NAME["mitigate-blank-only"]
+    ref = b.oracle(b.recording(), 0, 0, b.total())[0]
+    assert ref.blanked > 10 and ref.frames == 0 and len(np.unique(ref.i8)) > 30        # integer comparisons: no margin to keep
+
+
+@pytest.mark.parametrize("name", ["nulling-m3-b128-w3", "nulling-m2-b192-w2"])
+def test_nulling_weights_of_the_new_recordings_keep_their_distance_from_a_rounding_tie(name):
+    """as nulling_cases.check_margins: no scaled weight component within 1e-6 of a half-integer, in any block"""
+    c = S.BY_NAME[name]
+    ref = c.oracle(c.recording(), 0, 0, c.total())
+    for dt in c.dtypes:
+        assert ref[dt]["margin"] >= nulling_cases.MARGIN, (name, ref[dt]["margin"])
+        assert ref[dt]["owned"] == -(-c.total() // c.Lb)
+    print(name, "margin %.3g, clipped %d" % (ref["int8"]["margin"], ref["int8"]["clipped"]))
+    assert ref["int8"]["clipped"] > 50 and len(np.unique(ref["int8"]["wq"], axis=0)) > 3   # the gain clips, the weights move
+
+
+def test_the_other_new_recordings_are_worth_their_names():
+    for name in ("requant-u8", "requant-2sm"):
+        c = S.BY_NAME[name]
+        out, clipped, blocks, k = c.oracle(c.recording(), 0, 0, c.total())
+        assert blocks == -(-c.total() // c.Lb) and len(set(k.tolist())) > 3 and clipped > 0, (name, clipped, set(k.tolist()))
+    c = S.BY_NAME["cancel-two-sats"]
+    want, f32 = c.oracle(c.recording(), 0, 0, c.total())
+    x = c.recording()[0].view(np.int8)
+    assert np.max(np.abs(want - (x[0::2] + 1j * x[1::2]))) > 10.0 and 0 < np.max(np.abs(f32 - want)) / np.max(np.abs(want)) < 1e-5
+    for name in ("ingest-2sm-real", "ingest-1ob-iq", "ingest-s16-iq", "ddc-d5-t3"):
+        c = S.BY_NAME[name]
+        ref = c.oracle(c.recording(), 0, 0, c.total())
+        assert ref.dtype == np.complex64 and len(ref) == c.total() and len(np.unique(ref)) > (3 if name != "ingest-1ob-iq" else 2)
+
+
+def test_block_algebra_of_streaming_is_the_oracles():
+    """the adapters' needed / supported come from the oracles; the package's own (streaming.first_needed, out_end, owned_blocks) agree"""
+    for c in (S.BY_NAME["requant-2sm"], S.BY_NAME["nulling-m2-b192-w2"]):
+        unit = c.unit
+        for out in (0, 1, c.Lb - 1, c.Lb, c.W * c.Lb, c.W * c.Lb + 1, (c.W + 2) * c.Lb + 7, (1 << 32) + 5, (1 << 48) - 3):
+            assert streaming.first_needed(c.Lb, c.W, out) == c.needed(out, 1)[0]
+        for end in (0, c.W * c.Lb - 1, c.W * c.Lb, c.W * c.Lb + 1, 5 * c.Lb + 3, (1 << 32) + 3):
+            assert streaming.out_end(c.Lb, c.W, end, unit) == c.supported(0, end) == c.supported(c.Lb, end - c.Lb)
+
+
+# ---- requant_oracle.evaluate with in_first: every existing call gives what it gave
+def _evaluate_before(c, G, T, x, out_first=0, n_out=None):
+    """requant_oracle.evaluate as it was before it learnt in_first, kept here word for word as the yardstick"""
+    v = np.asarray(x).reshape(-1)
+    n = len(v) // 2
+    Lb, W = c["block"], c["window"]
+    total = RO.out_count(c, n)
+    n_out = total - out_first if n_out is None else n_out
+    assert out_first >= 0 and n_out >= 0 and out_first + n_out <= total and out_first % RO.unit(c) == 0 and n_out % RO.unit(c) == 0
+    G = np.asarray(G, dtype=np.float32)
+    if n_out == 0:
+        return np.zeros(0, dtype=np.uint8), 0, 0, np.zeros(0, dtype=np.uint8)
+    P = RO.block_powers(c, v)
+    nblocks = (out_first + n_out - 1) // Lb + 1
+    cum = [0]
+    for p in P.tolist():
+        cum.append(cum[-1] + p)
+    S_ = np.array([cum[W] if b < W else cum[b] - cum[b - W] for b in range(nblocks)], dtype=np.uint64)
+    k = RO.gain_indices(T, S_)
+    j = np.arange(out_first, out_first + n_out, dtype=np.int64)
+    g = np.repeat(G[k[j // Lb]], 2)
+    val = v[2 * out_first:2 * (out_first + n_out)].astype(np.float32) * g
+    kind = c["container"]
+    if kind == "f32":
+        out, clipped = val.astype("<f4").view(np.uint8), 0
+    elif kind in ("s8", "u8", "s16"):
+        lim = 32767 if kind == "s16" else 127
+        r = np.rint(val)
+        q = np.clip(r, -lim, lim)
+        clipped = int(np.count_nonzero(q != r))
+        if kind == "s16":
+            out = q.astype("<i2").view(np.uint8)
+        else:
+            out = (q.astype(np.int64) + (128 if kind == "u8" else 0)).astype(np.uint8 if kind == "u8" else np.int8).view(np.uint8)
+    else:
+        bits = c["bits"]
+        nlev = 1 << bits
+        f = np.floor(val * np.float32(0.5)) + np.float32(nlev // 2)
+        q = np.clip(f, 0, nlev - 1)
+        clipped = int(np.count_nonzero(q != f))
+        codes = np.asarray(c["enc"], dtype=np.int64)[q.astype(np.int64)]
+        per = 8 // bits
+        i = np.arange(per)
+        shift = (8 - bits * (i + 1)) if c["msb_first"] else bits * i
+        out = (codes.reshape(-1, per) << shift[None, :]).sum(axis=1).astype(np.uint8)
+    first_owned = -(-out_first // Lb)
+    owned = k[first_owned:nblocks]
+    return np.ascontiguousarray(out), clipped, len(owned), owned.astype(np.uint8)
+
+
+def _same_result(a, b):
+    return a[0].tobytes() == b[0].tobytes() and a[1:3] == b[1:3] and a[3].tobytes() == b[3].tobytes() and a[0].dtype == b[0].dtype == np.uint8
+
+
+@pytest.mark.parametrize("case", requant_cases.CASES, ids=requant_cases.case_id)
+def test_requant_oracle_gives_what_it_gave_on_every_committed_case(case):
+    name, msb, in_bits, Lb, W, n = case
+    fmt = requant_cases.requant.OutFormat(name, msb)
+    G, T = requant_cases.tables_for(fmt, Lb, W, in_bits)
+    c = requant_cases.ocfg(fmt, Lb, W, in_bits)
+    x = requant_cases.signal(n, 5, in_bits)
+    u = RO.unit(c)
+    assert _same_result(RO.evaluate(c, G, T, x), _evaluate_before(c, G, T, x))
+    assert _same_result(requant_cases.reference(*case), _evaluate_before(c, G, T, x))
+    # the ranges the GPU tests ask the oracle for: from a lane's run, from a byte, a tile, a cut inside the recording
+    for out_first, n_out in ((16, n // u * u - 16), (u, 4 * u), (Lb, 2 * Lb), (W * Lb + 4 * u, Lb + 4 * u), (0, 0)):
+        assert _same_result(RO.evaluate(c, G, T, x, out_first, n_out), _evaluate_before(c, G, T, x, out_first, n_out)), (out_first, n_out)
+    # ... and the same outputs from the input that needed() names, told where it begins
+    for out_first, n_out in (((W + 1) * Lb + 4 * u, Lb + 4 * u), ((W + 2) * Lb, n // u * u - (W + 2) * Lb), ((W + 3) * Lb - 4 * u, 8 * u)):
+        lo, end = RO.needed(c, out_first, n_out)
+        assert lo > 0 and lo % Lb == 0
+        assert _same_result(RO.evaluate(c, G, T, x[2 * lo:2 * end], out_first, n_out, lo), _evaluate_before(c, G, T, x, out_first, n_out)), (out_first, n_out)
+
+
+def test_requant_oracle_with_in_first_counts_blocks_by_the_absolute_index():
+    """far from zero nothing is a warm-up: the same bytes a multiple of Lb further give the same output, and a shift that is no multiple
+    of the block is another recording"""
+    c = S.BY_NAME["requant-2sm"]
+    lo, o, n, cnt = c.near_call()
+    x = c.cut(lo, lo + cnt)[0].view(np.int8)
+    near = RO.evaluate(c.ocfg, c.G, c.T, x, o, n, lo)
+    for s in (c.Lb, (1 << 32) // c.Lb * c.Lb, (1 << 48) // c.Lb * c.Lb - 5 * c.Lb):
+        assert _same_result(RO.evaluate(c.ocfg, c.G, c.T, x, o + s, n, lo + s), near)
+    with pytest.raises(AssertionError):
+        RO.evaluate(c.ocfg, c.G, c.T, x, o + 2, n, lo + 2)
+    # the warm-up applies to blocks below W only: block W + 1 from input that begins at block 1 sums blocks 1 .. W, not the first W present
+    Lb, W = c.Lb, c.W
+    whole = c.recording()[0].view(np.int8)
+    a = RO.evaluate(c.ocfg, c.G, c.T, whole[2 * Lb:], (W + 1) * Lb, Lb, Lb)
+    assert _same_result(a, _evaluate_before(c.ocfg, c.G, c.T, whole, (W + 1) * Lb, Lb))
+    with pytest.raises(AssertionError):
+        RO.evaluate(c.ocfg, c.G, c.T, whole[2 * Lb:], W * Lb, Lb, Lb)                  # block W needs block 0
