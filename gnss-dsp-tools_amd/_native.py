@@ -86,7 +86,7 @@ ERRORS = {0: "GACQ_OK", -1: "GACQ_ERR_BAD_ARG", -2: "GACQ_ERR_UNKNOWN_CODE", -3:
 
 # GACQ_OPT_* of include/gacq.h
 OPTIONS = {"fused_inner": 0, "fused_16k": 1, "lds_variant": 2, "lds_pch": 3, "split_pch": 4, "split_teams": 5, "fused_4k": 6, "split_dt": 7, "fe_generic": 8, "lds_ugroup": 9, "search1": 10, "bar_upload": 11, "watch_results": 12,
-           "tie_safe": 13, "tie_eps_ppb": 14, "tie_cap": 15, "fused_c128": 16, "split_mfma": 17}
+           "tie_safe": 13, "tie_eps_ppb": 14, "tie_cap": 15, "fused_c128": 16, "split_mfma": 17, "f4k_run": 18, "f4k_claim": 19}
 
 # name -> (restype, argtypes): every symbol include/gacq.h declares
 SYMBOLS = {
@@ -262,6 +262,8 @@ SYMBOLS = {
     "gacq_reset_stage_times": (ctypes.c_int, [ctypes.c_void_p]),
     "gacq_stage_name": (ctypes.c_char_p, [ctypes.c_int]),
     "gacq_debug_nco_indices": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, c_int_p]),
+    "gacq_debug_poison_rows": (ctypes.c_long, [ctypes.c_void_p, ctypes.c_long]),
+    "gacq_debug_f4k_map": (ctypes.c_long, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, c_int_p, ctypes.c_long]),
     "gacq_debug_fft_plans": (ctypes.c_int, [ctypes.c_void_p]),
     "gacq_acquire_int8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_double, c_double_p, ctypes.c_int,
                                          ctypes.c_size_t, c_int_p, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_void_p]),

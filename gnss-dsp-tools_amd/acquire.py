@@ -199,6 +199,11 @@ class Engine:
         nat.check(nat.lib.gacq_get_tie_stats(self._ctx, v), self._ctx)
         return {"ambiguous_pairs": v[0], "rows_reevaluated": v[1], "kept_fp32": v[2], "locations_changed": v[3]}
 
+    def poison_rows(self, row_after=-1):
+        """Test hook (gacq_debug_poison_rows): overwrite every row record the context holds with one that wins any Doppler scan, so that
+        a kernel which skips a record shows in the next search's results; row_after >= 0 makes the next search lose that record."""
+        return nat.check(nat.lib.gacq_debug_poison_rows(self._ctx, int(row_after)), self._ctx)
+
     def fft_plans(self):
         """gacq_debug_fft_plans: rocFFT plans this context has created (0 on the default engines' path, code spectra included)."""
         return nat.check(nat.lib.gacq_debug_fft_plans(self._ctx), self._ctx)

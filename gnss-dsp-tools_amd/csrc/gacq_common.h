@@ -24,6 +24,9 @@ struct RowRec {
   double sum;    // sum_k q[k]  (for the max/mean metric)
 };
 
+// test hook (gacq_debug_poison_rows): a record that wins any Doppler scan it takes part in
+constexpr RowRec kPoisonRow = {1.0e30f, 1234, 1.0};
+
 // Tie-safe peak locations (gacq_tiesafe.hip).  The reference takes argmax and the strict-'>' Doppler scan in fp64
 // (acquire-gps-l1.py:34-39); the fp32 engines can land on another lag / bin when two candidates are closer than their rounding
 // error.  Every row reduction therefore also reports whether a second lag comes within `tie_scale` = 1 - eps of the row maximum
@@ -82,7 +85,10 @@ struct gacq_ctx {
   gacq::DevBuf tab, xstage, x32, X, Y, rows, freq, fset, items, out_peaks, d0, partial, fe_a, fe_b, fe_taps, chunk_peaks;
   gacq::DevBuf tie, tie_scratch, tie_q, tie_split, tie_done2;   // tie-safe re-evaluation: counters + lists, complex128 row scratch, per-block magnitude rows
   int tie_cap = 0;                     // list capacity the `tie` buffer was laid out for
-  long opt[GACQ_NOPTS] = {1, 1, -1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 1, 1, 8000, 0, 1, 0};   // gacq_set_option values (defaults documented in include/gacq.h)
+  gacq::DevBuf f4k_cnt;                // lds_fused4k_kernel, claimed work: the eight queue counters
+  long poison_row = -1;                // test hook (gacq_debug_poison_rows): row record the next search overwrites before its Doppler scan
+  int cu_count = 0;                    // compute units of the device (0 = not asked yet): sizes the unit runs of lds_fused4k_kernel
+  long opt[GACQ_NOPTS] = {1, 1, -1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 1, 1, 8000, 0, 1, 0, 1, 1};   // gacq_set_option values (defaults documented in include/gacq.h)
   gacq::DevBuf pin_x, pin_peaks;       // pinned host staging for the host-buffer entry point (gacq_search)
   gacq::DevBuf acq_in, acq_x;          // gacq_acquire_int8: the raw int8 block and its front-end output on the device
   gacq::DevBuf pin_fold[2];            // gacq_fold_dev: pinned staging of the parameter block, two slots in turn
@@ -260,6 +266,9 @@ int r16_debug_nco(gacq_ctx* ctx, int n, const double* d_freq, bool fused, int* d
 // test hook (gacq_debug_nco_indices): the forward kernel's own NCO index expression for one row, d_idx[N]; fused (r32 / r16): the
 // one-kernel N = 16384 search
 int lds_debug_nco(gacq_ctx* ctx, int n, const double* d_freq, int* d_idx);
+// test hook (gacq_debug_f4k_map): the block-to-work map of lds_fused4k_kernel walked on the host; returns the work items visited
+long lds_debug_f4k_map(int nepoch, int D, int nchunk, int run, int cus, int* info, int* work, long cap);
+long lds_debug_f4k_queues(int nepoch, int D, int nchunk, long claim, int cus, int* info, int* work, long cap);
 int split_debug_nco(gacq_ctx* ctx, int N, int n, const double* d_freq, int* d_idx);
 
 // front-end carrier wipe-off alone (gacq_frontend.hip): int8 I/Q on the device -> complex64, fixed-point table NCO

@@ -49,6 +49,15 @@ __device__ __forceinline__ v2 cmul(v2 a, v2 b) {
       : "v"(a), "v"(b));
   return r;
 }
+// a*conj(b) with the conjugation in the neg modifiers: the bits of cmul(a, v2{b.x, -b.y})
+__device__ __forceinline__ v2 cmul_conj(v2 a, v2 b) {
+  v2 t, r;
+  asm("v_pk_mul_f32 %0, %2, %3 op_sel:[1,1] op_sel_hi:[1,0]\n\t"
+      "v_pk_fma_f32 %1, %2, %3, %0 op_sel:[0,0,0] op_sel_hi:[0,1,1] neg_hi:[0,1,0]"
+      : "=&v"(t), "=v"(r)
+      : "v"(a), "v"(b));
+  return r;
+}
 // a*w with w a compile-time constant held in an SGPR pair (one constant-bus operand per instruction)
 __device__ __forceinline__ v2 cmul_k(v2 a, v2 w) {
   v2 t, r;

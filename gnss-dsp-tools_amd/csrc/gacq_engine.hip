@@ -555,7 +555,7 @@ void gacq_destroy(gacq_ctx* ctx) {
     if (kv.second.work) (void)hipFree(kv.second.work);
   }
   for (auto& ev : ctx->pending) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
-  DevBuf* bufs[] = {&ctx->tab, &ctx->xstage, &ctx->x32, &ctx->X, &ctx->Y, &ctx->rows, &ctx->freq, &ctx->fset, &ctx->items, &ctx->out_peaks, &ctx->d0, &ctx->partial, &ctx->fe_a, &ctx->fe_b, &ctx->fe_taps, &ctx->chunk_peaks, &ctx->tie, &ctx->tie_scratch, &ctx->tie_q, &ctx->tie_split, &ctx->tie_done2, &ctx->acq_in, &ctx->acq_x};
+  DevBuf* bufs[] = {&ctx->tab, &ctx->xstage, &ctx->x32, &ctx->X, &ctx->Y, &ctx->rows, &ctx->freq, &ctx->fset, &ctx->items, &ctx->out_peaks, &ctx->d0, &ctx->partial, &ctx->fe_a, &ctx->fe_b, &ctx->fe_taps, &ctx->chunk_peaks, &ctx->tie, &ctx->tie_scratch, &ctx->tie_q, &ctx->tie_split, &ctx->tie_done2, &ctx->acq_in, &ctx->acq_x, &ctx->f4k_cnt};
   for (DevBuf* b : bufs) if (b->p) (void)hipFree(b->p);
   if (ctx->pin_x.p) (void)hipHostFree(ctx->pin_x.p);
   if (ctx->pin_peaks.p) (void)hipHostFree(ctx->pin_peaks.p);
@@ -605,7 +605,7 @@ int gacq_set_workspace_limit(gacq_ctx* ctx, size_t bytes) {
 int gacq_set_option(gacq_ctx* ctx, int option, long value) {
   if (!ctx || option < 0 || option >= GACQ_NOPTS) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_set_option: unknown option %d", option);
   // accepted range per option (GACQ_OPT_* order): switches 0/1(/2), counts bounded by what the kernels' index arithmetic carries
-  static const long kMax[GACQ_NOPTS] = {1, 1, 1000, 4096, 4096, 4, 2, 3, 1, 64, 1, 1, 1, 1, 1000000000L, 1L << 24, 1, 1};
+  static const long kMax[GACQ_NOPTS] = {1, 1, 1000, 4096, 4096, 4, 2, 3, 1, 64, 1, 1, 1, 1, 1000000000L, 1L << 24, 1, 1, 4096, 65536};
   const long lo = (option == GACQ_OPT_LDS_VARIANT) ? -1 : 0;
   if (value < lo || value > kMax[option])
     return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_set_option: value %ld out of range [%ld, %ld] for option %d", value, lo, kMax[option], option);
@@ -1047,6 +1047,11 @@ int launch_search(gacq_sig* sig, XSrc xs, const float2* d_x, size_t nsamp, int n
         rc = timed(ctx, 1, [&] { return fft_exec(ctx, N, rows_x, false, X); });
     }
     if (rc != GACQ_OK) return rc;
+    if (ctx->poison_row >= 0) {      // test hook (gacq_debug_poison_rows): one record as a kernel that skipped it would have left it
+      if ((size_t)ctx->poison_row < (size_t)ne * P * D)
+        GACQ_HIP(ctx, hipMemcpyAsync(rows + ctx->poison_row, &kPoisonRow, sizeof(RowRec), hipMemcpyHostToDevice, st));
+      ctx->poison_row = -1;
+    }
     if (plan.form != Form::Lds && !plan.fused()) {
       // correlation workspace: chunks of whole (e,p,d) groups, B rows each
       const long groups = (long)ne * P * D;
@@ -1516,6 +1521,26 @@ int gacq_scan_int8_dev(gacq_sig* sig, const void* d_iq_int8, long long nsamp_ava
 int gacq_debug_fft_plans(gacq_ctx* ctx) {
   if (!ctx) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_debug_fft_plans: bad argument");
   return (int)ctx->plans.size();
+}
+
+long gacq_debug_poison_rows(gacq_ctx* ctx, long row_after) {
+  if (!ctx) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_debug_poison_rows: ctx is NULL");
+  GACQ_DEVICE(ctx);
+  const size_t n = ctx->rows.p ? ctx->rows.cap / sizeof(RowRec) : 0;
+  if (n) {
+    const std::vector<RowRec> fill(n, kPoisonRow);
+    GACQ_HIP(ctx, hipMemcpyAsync(ctx->rows.p, fill.data(), n * sizeof(RowRec), hipMemcpyHostToDevice, ctx->stream));
+    GACQ_HIP(ctx, hipStreamSynchronize(ctx->stream));      // `fill` is pageable host memory
+  }
+  ctx->poison_row = row_after;
+  return (long)n;
+}
+
+long gacq_debug_f4k_map(int nepoch, int nbins, int nchunk, int run, int cus, int* info, int* work, long cap) {
+  if (nepoch <= 0 || nbins <= 0 || nchunk <= 0 || run < -65536 || cus <= 0 || cap < 0 || (long)nepoch * nbins * nchunk > (1L << 28))
+    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_debug_f4k_map: bad argument");
+  if (run < 0) return lds_debug_f4k_queues(nepoch, nbins, nchunk, -run, cus, info, work, cap);
+  return lds_debug_f4k_map(nepoch, nbins, nchunk, run, cus, info, work, cap);
 }
 
 int gacq_debug_nco_indices(gacq_sig* sig, int kernel, double doppler, double bias_hz, int* idx_out) {

@@ -47,6 +47,10 @@ __device__ __forceinline__ void make_powers(v2 (&pw)[15], v2 w1) {
 //   FUSED (a ROWLOOP)   the fused kernel's item loop: the pass-1 powers too come precomputed, in registers (*pa, already conjugated),
 //                       and the last radix-4 layer leaves its outputs planar in *pl instead of in v (dft16_inv_planar, gacq_cplx.h):
 //                       pl[j] = (re X[t + 256 j], re X[t + 256 (j + 8)]), pl[8 + j] the imaginary parts
+//   RESIDENT (forward)  the fused kernel's forward transform: both passes' powers are the conjugates of the inverse transform's resident
+//                       ones (*pa in registers, tb2 in LDS), multiplied through the neg modifiers (cmul_conj).  cmul is sign-symmetric
+//                       under IEEE rounding -- conj(cmul(a, b)) and cmul(conj a, conj b) are the same bits -- so these are the values the
+//                       plain form rebuilds from wa / wb with its two product trees, 28 complex products per transform less
 // Rising wave priority through the segments of a 4096-point row (the caller resets it to GACQ_F4K_P4 at the top of its row loop):
 // after the exchange-1 writes | after the exchange-2 writes | after the exchange-2 reads have been issued.  The four
 // waves of a SIMD belong to four independent workgroups; letting the one that is furthest into its row issue first keeps the workgroups
@@ -71,11 +75,12 @@ __device__ __forceinline__ void make_powers(v2 (&pw)[15], v2 w1) {
 #define GACQ_F4K_P0 -1      // at the first radix-16 pass (sweeps only)
 #endif
 #define F4K_PRIO(n) do { if ((n) >= 0) asm volatile("s_setprio %0" :: "n"(n) : "memory"); } while (0)
-template <bool INV, bool ROWLOOP = false, bool FUSED = false>
+template <bool INV, bool ROWLOOP = false, bool FUSED = false, bool RESIDENT = false>
 __device__ __forceinline__ void fft4096(v2 (&v)[kR], v2* lds, v2 wa, v2 wb, const v2* tb2 = nullptr, const v2 (*pa)[15] = nullptr,
                                         v2 (*pl)[kR] = nullptr) {
   static_assert(INV || !ROWLOOP, "table and priorities: inverse transform only");
   static_assert(ROWLOOP || !FUSED, "the fused item loop is a row loop");
+  static_assert(!RESIDENT || (!INV && !ROWLOOP), "conjugates of the resident powers: forward transform only");
   const int t = threadIdx.x;
   if (INV) { wa.y = -wa.y; wb.y = -wb.y; }
   F4K_PRIO(ROWLOOP ? GACQ_F4K_P0 : -1);
@@ -83,6 +88,9 @@ __device__ __forceinline__ void fft4096(v2 (&v)[kR], v2* lds, v2 wa, v2 wb, cons
   if (FUSED) {
 #pragma unroll
     for (int k = 1; k < kR; k++) v[rev16(k)] = cmul(v[rev16(k)], (*pa)[k - 1]);
+  } else if (RESIDENT) {
+#pragma unroll
+    for (int k = 1; k < kR; k++) v[rev16(k)] = cmul_conj(v[rev16(k)], (*pa)[k - 1]);
   } else apply_powers(v, wa);
   {  // exchange 1: (n0,n1;k0) -> (n0,k0;n1)
     const int wbase = (t & 15) + 256 * (t >> 4);
@@ -97,6 +105,9 @@ __device__ __forceinline__ void fft4096(v2 (&v)[kR], v2* lds, v2 wa, v2 wb, cons
   if (ROWLOOP) {
 #pragma unroll
     for (int k = 1; k < kR; k++) v[rev16(k)] = cmul(v[rev16(k)], LDS_LD(tb2[16 * (k - 1)]));
+  } else if (RESIDENT) {
+#pragma unroll
+    for (int k = 1; k < kR; k++) v[rev16(k)] = cmul_conj(v[rev16(k)], LDS_LD(tb2[16 * (k - 1)]));
   } else apply_powers(v, wb);
   __syncthreads();   // all exchange-1 reads done before the buffer is reused
   {  // exchange 2: (n0,k0;k1) -> (k0,k1;n0)
@@ -421,11 +432,156 @@ __global__ __launch_bounds__(kBlock, 2) void lds_correlate_kernel(const float2* 
 // over with agent-scope stores and an arrival counter -- measured slower than the three short launches it replaced (21.8 us of kernel
 // against 6.8 + 12.3 + 6.5 us whose launch latencies overlap, profiles/r03_single_search_latency.log) and had no hook for the tie-safe
 // re-evaluation; removed in round 6.)
+//
+// Unit runs.  A workgroup walks `run` consecutive work items (one work item = one (epoch, Doppler bin, item chunk): what a workgroup
+// used to be) and pays what does not depend on the work item once: the two twiddle loads, the pass-1 powers pwa, the pass-2 table
+// s_tw2, the lane offset and the decode of its block index.  Per work item, in the same order and the same bits as before: x window,
+// NCO mix, forward transform, item loop, ring flush.  The forward transform takes its powers from pwa / s_tw2 (fft4096's RESIDENT form).
+// Nothing between two work items needs a barrier of its own: the last row's closing barrier orders its exchange-2 reads before the next
+// forward transform's exchange-1 writes, and no wave writes ring slot 0 again before it has passed that transform's barriers, which wave
+// 0 reaches only after its flush.
+//
+// GACQ_F4K_STAMPS (a diagnostic variant built by tools/build_variant.sh for tools/f4k_stamps.py, never the product library): lane 0 of
+// every workgroup stores the 100 MHz wall clock at kernel entry, before its first row and after its last row, and where it ran
+// (HW_ID, XCC_ID), into a buffer the tool hands over with gacq_debug_f4k_stamps.
+#ifdef GACQ_F4K_STAMPS
+__device__ unsigned long long* g_f4k_stamps;      // [g_f4k_nstamps][4]: entry, first row, end, XCC_ID << 32 | HW_ID
+__device__ unsigned g_f4k_nstamps;
+#define F4K_STAMP(slot) do { if (threadIdx.x == 0 && blockIdx.x < g_f4k_nstamps) g_f4k_stamps[4ul * blockIdx.x + (slot)] = (unsigned long long)wall_clock64(); } while (0)
+#else
+#define F4K_STAMP(slot) do { } while (0)
+#endif
+struct F4kMap {
+  int E, D, nchunk;      // epochs, Doppler bins, item chunks per (epoch, bin)
+  int run;               // work items per workgroup, >= 1
+  int by_epoch;          // 1: all work of epoch e on XCD e % 8, a run stays inside its epoch; 0: (epoch, bin) units dealt round-robin, a
+                         // run walks the units of its own XCD
+  int nruns;             // runs per epoch (by_epoch) or per XCD
+  int claim;             // 1: persistent workgroups take their work items from eight counters, one queue per XCD (below)
+  unsigned grid;
+};
+struct F4kPos {
+  unsigned e, d, c;      // epoch, Doppler bin, item chunk
+  int left;              // work items of the run still to do, this one included; <= 0: none
+};
+
+// run = 0 picks the fewest runs that still leave four rounds of resident workgroups (4 per CU) and cuts them to equal lengths; any
+// run is capped at the work items of one epoch
+__host__ __device__ inline F4kMap f4k_map(int E, int D, int nchunk, int run, int cus) {
+  F4kMap m;
+  m.E = E; m.D = D; m.nchunk = nchunk;
+  m.claim = 0;
+  m.by_epoch = E >= 64 ? 1 : 0;
+  const long per_epoch = (long)D * nchunk;
+  const long span = m.by_epoch ? per_epoch : (((long)E * D + 7) / 8) * nchunk;      // work items a run index counts through
+  const long groups = m.by_epoch ? 8L * ((E + 7) / 8) : 8;                         // ... and how many such spans the grid has
+  const long cap = per_epoch < span ? per_epoch : span;
+  long u = run;
+  if (u <= 0) {
+    u = 1;
+    const long want = 16L * cus;
+    for (long k = cap; k > 1; k--)
+      if (groups * ((span + k - 1) / k) >= want) { u = k; break; }
+    const long nruns = (span + u - 1) / u;
+    u = (span + nruns - 1) / nruns;      // the same number of runs, of as equal lengths as they come (40 work items: 4 x 10, not 3 x 13 + 1)
+  }
+  if (u > cap) u = cap;
+  m.run = (int)u;
+  m.nruns = (int)((span + u - 1) / u);
+  m.grid = (unsigned)(groups * m.nruns);
+  return m;
+}
+
+// first work item of workgroup `block`
+__host__ __device__ inline F4kPos f4k_first(const F4kMap& m, unsigned block) {
+  F4kPos p;
+  const unsigned xcd = block & 7, j = block >> 3;      // workgroup b runs on XCD b % 8
+  const unsigned w0 = (j % (unsigned)m.nruns) * (unsigned)m.run;
+  p.c = w0 % (unsigned)m.nchunk;
+  if (m.by_epoch) {
+    p.e = (j / (unsigned)m.nruns) * 8 + xcd;
+    p.d = w0 / (unsigned)m.nchunk;
+    const int span = m.D * m.nchunk;
+    p.left = p.e < (unsigned)m.E ? (m.run < span - (int)w0 ? m.run : span - (int)w0) : 0;
+  } else {
+    const unsigned units = (unsigned)m.E * (unsigned)m.D;
+    const unsigned u = (w0 / (unsigned)m.nchunk) * 8 + xcd;
+    p.e = u / (unsigned)m.D;
+    p.d = u % (unsigned)m.D;
+    const int span = (int)((units + 7) / 8) * m.nchunk;
+    p.left = u < units ? (m.run < span - (int)w0 ? m.run : span - (int)w0) : 0;
+  }
+  return p;
+}
+
+// the run's next work item (no division)
+__host__ __device__ inline void f4k_next(const F4kMap& m, F4kPos& p) {
+  p.left--;
+  if (++p.c < (unsigned)m.nchunk) return;
+  p.c = 0;
+  if (m.by_epoch) { p.d++; return; }
+  p.d += 8;
+  while (p.d >= (unsigned)m.D) { p.d -= (unsigned)m.D; p.e++; }
+  if (p.e >= (unsigned)m.E) p.left = 0;      // the XCD's last units do not exist when E x D is no multiple of 8
+}
+
+// Claimed work.  The grid is one workgroup per resident slot (4 per CU) and stays for the whole launch; the work items are eight queues,
+// queue q = the work the static map gives to the blocks with b % 8 == q (so a queue's epochs still meet in one L2), in the static map's
+// order.  Workgroup b starts with item b / 8 of queue b % 8 and then takes the next unclaimed one with an atomic add on the queue's
+// counter (the host sets the counters to grid / 8 before the launch); when its queue is empty it takes from the next queue, and so on
+// round the eight: an XCD that runs a few per cent faster than another (they do) helps out instead of standing idle at the end.  The
+// set-up is paid once per workgroup as in a run, but a workgroup that is slow takes fewer items, so no slot waits for another at the
+// end of the launch for longer than one work item -- what a fixed run longer than 1 loses.
+__host__ __device__ inline unsigned f4k_queue_len(const F4kMap& m, unsigned q) {
+  const unsigned heads = m.by_epoch ? (unsigned)m.E : (unsigned)m.E * (unsigned)m.D;      // epochs or units, dealt round the queues
+  const unsigned per_head = m.by_epoch ? (unsigned)m.D * (unsigned)m.nchunk : (unsigned)m.nchunk;
+  return q < heads ? ((heads - q + 7) / 8) * per_head : 0;
+}
+// item w of queue q
+__host__ __device__ inline F4kPos f4k_item(const F4kMap& m, unsigned q, unsigned w) {
+  F4kPos p;
+  p.left = 1;
+  p.c = w % (unsigned)m.nchunk;
+  const unsigned r = w / (unsigned)m.nchunk;
+  if (m.by_epoch) {
+    p.e = (r / (unsigned)m.D) * 8 + q;
+    p.d = r % (unsigned)m.D;
+  } else {
+    const unsigned u = r * 8 + q;
+    p.e = u / (unsigned)m.D;
+    p.d = u % (unsigned)m.D;
+  }
+  return p;
+}
+constexpr int kF4kCntPitch = 16;      // dwords between two queue counters: one 64-byte line each
+// Option f4k_claim: 0 = the static map; 1 = claimed work with one workgroup per resident slot (4 per CU) when the longest queue has
+// more work items than that gives it workgroups, else the static map (which is then the same thing); n > 1 = claimed work with n
+// workgroups (rounded up to a multiple of 8), whatever the shape -- tests and sweeps.  True: claimed work, map.grid is its grid.
+inline bool f4k_claim_grid(F4kMap& m, long claim, int cus) {
+  if (claim <= 0) return false;
+  const unsigned per_queue = claim == 1 ? (unsigned)(4 * cus) / 8 : (unsigned)((claim + 7) / 8);
+  if (per_queue == 0 || (claim == 1 && f4k_queue_len(m, 0) <= per_queue)) return false;
+  m.claim = 1;
+  m.grid = 8 * per_queue;
+  return true;
+}
+// One lane takes the next unclaimed work item, from queue (q0 + q_off) % 8 on; q_off counts the queues it has found empty.  q_out = 8: none.
+__device__ __forceinline__ void f4k_claim(unsigned* cnt, const F4kMap& m, unsigned q0, unsigned& q_off, unsigned& q_out, unsigned& w_out) {
+  q_out = 8;
+  w_out = 0;
+  for (; q_off < 8; q_off++) {
+    const unsigned q = (q0 + q_off) & 7, len = f4k_queue_len(m, q);
+    if (len <= gridDim.x / 8) continue;      // nothing beyond its workgroups' first items
+    const unsigned w = atomicAdd(cnt + q * kF4kCntPitch, 1u);
+    if (w < len) { q_out = q; w_out = w; return; }
+  }
+}
+
 __global__ __launch_bounds__(kBlock, 4) void lds_fused4k_kernel(const float2* __restrict__ x, size_t epoch_stride,
                                                                 const float2* __restrict__ C, const int* __restrict__ items,
                                                                 const double* __restrict__ freq, const float2* __restrict__ nco_tab,
-                                                                const float2* __restrict__ tw, RowRec* __restrict__ rows, int E, int P,
-                                                                int D, int pch, int nchunk, int by_epoch, float tie_scale) {
+                                                                const float2* __restrict__ tw, RowRec* __restrict__ rows, F4kMap map, int P,
+                                                                int pch, float tie_scale, unsigned* __restrict__ cnt) {
   constexpr int kRing = 32;                           // item slots between two flushes: a power of two, at most 64 (one lane each)
   static_assert(kRing >= 1 && kRing <= 64 && (kRing & (kRing - 1)) == 0, "kRing");
   __shared__ v2 lds[kLdsElems];
@@ -436,22 +592,41 @@ __global__ __launch_bounds__(kBlock, 4) void lds_fused4k_kernel(const float2* __
   // Placement (workgroup b runs on XCD b % 8).  Batches: all D x nchunk workgroups of an epoch go to XCD e % 8, so the epoch's
   // sample block is fetched into one L2 instead of eight (round 2: 8.3 x the compulsory fetch).  Few epochs: (epoch, Doppler)
   // units are dealt round-robin as in lds_correlate_kernel, so that a single-epoch search still fills all eight XCDs.
-  const int xcd = blockIdx.x & 7;
-  const unsigned j = blockIdx.x >> 3;
-  unsigned u;
-  if (by_epoch) {
-    const unsigned per_epoch = (unsigned)D * (unsigned)nchunk;
-    const unsigned e8 = (j / per_epoch) * 8 + xcd;
-    if (e8 >= (unsigned)E) return;
-    u = e8 * (unsigned)D + (j % per_epoch) / (unsigned)nchunk;
+  // The map itself is f4k_first / f4k_next above.
+  __shared__ unsigned s_claim[2];                     // claimed work: the workgroup's next work item (queue, index in the queue); queue 8 = none
+  const unsigned q0 = blockIdx.x & 7;
+  const unsigned len0 = f4k_queue_len(map, q0);
+  unsigned q_off = len0 > gridDim.x / 8 ? 0 : 1;      // lane 0: queues found empty
+  F4kPos pos;
+  if (map.claim) {
+    if ((blockIdx.x >> 3) < len0) pos = f4k_item(map, q0, blockIdx.x >> 3);
+    else {                                            // fewer work items in the queue than workgroups: take from the other queues at once
+      if (t == 0) {
+        unsigned q, w;
+        f4k_claim(cnt, map, q0, q_off, q, w);
+        s_claim[0] = q;
+        s_claim[1] = w;
+      }
+      __syncthreads();
+      const unsigned q = (unsigned)__builtin_amdgcn_readfirstlane((int)s_claim[0]), w = (unsigned)__builtin_amdgcn_readfirstlane((int)s_claim[1]);
+      if (q >= 8) return;
+      pos = f4k_item(map, q, w);
+    }
   } else {
-    u = (j / (unsigned)nchunk) * 8 + xcd;
-    if (u >= (unsigned)E * (unsigned)D) return;
+    pos = f4k_first(map, blockIdx.x);
+    if (pos.left <= 0) return;
   }
-  const long e = u / (unsigned)D;
-  const int d = (int)(u % (unsigned)D);
-  const int p0 = (int)(j % (unsigned)nchunk) * pch;
-  const int p1 = min(P, p0 + pch);
+  F4K_STAMP(0);
+#ifdef GACQ_F4K_STAMPS
+  bool first_row = true;
+  if (t == 0 && blockIdx.x < g_f4k_nstamps) {
+    unsigned hw, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    g_f4k_stamps[4ul * blockIdx.x + 3] = ((unsigned long long)xcc << 32) | hw;
+  }
+#endif
+  const int D = map.D;
   v2 wa = ld2(tw + t), wb = ld2(tw + 16 * (t & 15));
   // The pass-2 twiddle powers of the inverse transform, conj(W_256^c)^k for the 16 lane classes
   // c = t & 15, are built once per workgroup with the product tree of apply_powers (same values, so the records stay
@@ -464,75 +639,111 @@ __global__ __launch_bounds__(kBlock, 4) void lds_fused4k_kernel(const float2* __
 #pragma unroll
     for (int k = 0; k < 15; k++) s_tw2[16 * k + t] = pw[k];
   }
-  v2 xr[kR];
   const unsigned lane_off = (unsigned)t * 16u;
-  {
-    const double f = freq[d];
-    const float2* src = x + e * epoch_stride;
-    v2 v[kR], w[kR];
-#pragma unroll
-    for (int jj = 0; jj < kR; jj++) {
-      const int i = t + 256 * jj;
-      const int k = nco_index(f, i);                  // gnsstools/nco.py:6-9
-      v[jj] = ld2(src + i);
-      w[jj] = ld2(nco_tab + k);
-    }
-#pragma unroll
-    for (int jj = 0; jj < kR; jj++) v[jj] = cmul(v[jj], w[jj]);
-    fft4096<false>(v, lds, wa, wb);
-#pragma unroll
-    for (int jj = 0; jj < kR; jj++) { const v2 a = v[rev16(jj)]; xr[jj] = v2{a.x, -a.y}; }      // np.conj(fft.fft(b))  acquire-gps-l1.py:32
-    __syncthreads();                                  // the forward transform's exchange-2 reads are complete
-  }
   const float inv_n = 1.0f / (float)kLdsN;
   v2 pwa[15];
   make_powers(pwa, v2{wa.x, -wa.y});                  // conjugate: inverse transform
-  for (int p = p0; p < p1; p++) {
-    F4K_PRIO(GACQ_F4K_P4);
-    // No row reads wb any more (pass 2 takes its powers from s_tw2).  The empty statement stays because it pins wb's two registers
-    // through the loop, and the register assignment of the whole kernel -- the one every measurement above was made with -- depends on
-    // it: without it the kernel compiles to other instructions (tools/isa_diff.py).
-    asm volatile("" : "+v"(wb.x), "+v"(wb.y));
-    v2 v[kR];
-    const __amdgpu_buffer_rsrc_t cres = row_rsrc(C + (long)items[p] * kLdsN);
+  for (;;) {
+    // claimed work: the atomic for the next work item is issued here and its result is looked at behind the forward transform
+    unsigned w_ahead = 0;
+    if (map.claim && t == 0 && q_off == 0) w_ahead = atomicAdd(cnt + q0 * kF4kCntPitch, 1u);
+    const long e = pos.e;
+    const int d = (int)pos.d;
+    const int p0 = (int)pos.c * pch;
+    const int p1 = min(P, p0 + pch);
+    v2 xr[kR];
+    {
+      const double f = freq[d];
+      const float2* src = x + e * epoch_stride;
+      v2 v[kR], w[kR];
+      // The sample numbers are formed again for every work item: as loop invariants the compiler carries the sixteen (double)i across
+      // the run, 32 registers the item loop does not have.
+      int ti = t;
+      asm volatile("" : "+v"(ti));
 #pragma unroll
-    for (int jp = 0; jp < kR / 2; jp++) ld_pair(cres, lane_off, jp, v[2 * jp], v[2 * jp + 1]);
+      for (int jj = 0; jj < kR; jj++) {
+        const int i = ti + 256 * jj;
+        const int k = nco_index(f, i);                  // gnsstools/nco.py:6-9
+        v[jj] = ld2(src + i);
+        w[jj] = ld2(nco_tab + k);
+      }
 #pragma unroll
-    for (int jj = 0; jj < kR; jj++) v[jj] = cmul(v[jj], xr[jj]);
-    // lane t holds lags t + 256 k.  The 1/N of ifft is a power of two: applied once to the reduced values.
-    float m[kR];
-    // Epilogue: the transform's last layer delivers (re, re) / (im, im) pairs of lags k and k + 8, so that two
-    // squared magnitudes cost one v_pk_mul_f32 + one v_pk_fma_f32 (norm2's two roundings each) instead of two v_mul_f32 + two
-    // v_fmac_f32; m[k] is still lag t + 256 k (a renaming).  The sum over k stays the sequential chain, and the wave reductions
-    // combine the four rows on DPP too.  Every value is the same bits as with the (re, im) epilogue it replaced.  23 VALU
-    // instructions a row less (439 -> 416, SQ_INSTS_VALU agrees); headline step 1.012 x in the medians, every run above every run of the loop before it on two
-    // boxes (profiles/r15_fused4k_epilogue_ab.log).
-    v2 pl[kR];
-    fft4096<true, true, true>(v, lds, wa, wb, s_tw2 + (t & 15), &pwa, &pl);
+      for (int jj = 0; jj < kR; jj++) v[jj] = cmul(v[jj], w[jj]);
+      fft4096<false, false, false, true>(v, lds, wa, wb, s_tw2 + (t & 15), &pwa);
 #pragma unroll
-    for (int k = 0; k < kR / 2; k++) {
-      const v2 q = norm2_planar(pl[k], pl[k + kR / 2]);
-      m[k] = __builtin_amdgcn_sqrtf(q.x);                           // np.absolute(ifft(...)) * N
-      m[k + kR / 2] = __builtin_amdgcn_sqrtf(q.y);
+      for (int jj = 0; jj < kR; jj++) { const v2 a = v[rev16(jj)]; xr[jj] = v2{a.x, -a.y}; }      // np.conj(fft.fft(b))  acquire-gps-l1.py:32
+      if (map.claim && t == 0) {
+        unsigned q = q0, w = w_ahead;
+        if (q_off != 0 || w >= len0) {                  // own queue empty: the others, one atomic each (only at the end of the launch)
+          if (q_off == 0) q_off = 1;
+          f4k_claim(cnt, map, q0, q_off, q, w);
+        }
+        s_claim[0] = q;                                 // read behind the item loop; written again only behind the next transform's barriers
+        s_claim[1] = w;
+      }
+      __syncthreads();                                  // the forward transform's exchange-2 reads are complete
     }
-    float sum_f = m[0];
+#ifdef GACQ_F4K_STAMPS
+    if (first_row) { F4K_STAMP(1); first_row = false; }
+#endif
+    for (int p = p0; p < p1; p++) {
+      F4K_PRIO(GACQ_F4K_P4);
+      // No row reads wb any more (pass 2 takes its powers from s_tw2).  The empty statement stays because it pins wb's two registers
+      // through the loop, and the register assignment of the whole kernel -- the one every measurement above was made with -- depends on
+      // it: without it the kernel compiles to other instructions (tools/isa_diff.py).
+      asm volatile("" : "+v"(wb.x), "+v"(wb.y));
+      v2 v[kR];
+      // (The item number one row ahead -- its scalar load off the row's critical path -- measured no different: 5.29-5.32 against
+      // 5.29-5.32 ms, profiles/r17_fused4k_claimed_work_ab.log.  Not built in.)
+      const __amdgpu_buffer_rsrc_t cres = row_rsrc(C + (long)items[p] * kLdsN);
 #pragma unroll
-    for (int k = 1; k < kR; k++) sum_f += m[k];
-    float wmaxf;
-    unsigned widx;
-    wave_first_max<kR, wave_max_u32_bcast>(m, (unsigned)__builtin_amdgcn_readfirstlane(t & ~63), 1u, 256u, tie_scale, wmaxf, widx);
-    const float wsum = wave_add_f32_bcast(sum_f * inv_n);
-    const unsigned wmax = __builtin_bit_cast(unsigned, wmaxf * inv_n);
-    const int slot = (p - p0) & (kRing - 1);
-    if ((t & 63) == 0) { s_rpeak[slot][t >> 6] = __builtin_bit_cast(float, wmax); s_ridx[slot][t >> 6] = (int)widx; s_rsum[slot][t >> 6] = wsum; }
-    lds_barrier();     // also orders this item's exchange-2 reads before the next item's exchange-1 writes
-    if ((slot == kRing - 1 || p == p1 - 1) && t <= slot) {
-      RowRec r;
-      combine_tagged(kBlock / 64, [&](int w) { return s_rpeak[t][w]; }, [&](int w) { return s_ridx[t][w]; }, tie_scale, r.peak, r.idx);
-      r.sum = (((double)s_rsum[t][0] + (double)s_rsum[t][1]) + (double)s_rsum[t][2]) + (double)s_rsum[t][3];
-      rows[(e * P + (p - slot + t)) * (long)D + d] = r;
+      for (int jp = 0; jp < kR / 2; jp++) ld_pair(cres, lane_off, jp, v[2 * jp], v[2 * jp + 1]);
+#pragma unroll
+      for (int jj = 0; jj < kR; jj++) v[jj] = cmul(v[jj], xr[jj]);
+      // lane t holds lags t + 256 k.  The 1/N of ifft is a power of two: applied once to the reduced values.
+      float m[kR];
+      // Epilogue: the transform's last layer delivers (re, re) / (im, im) pairs of lags k and k + 8, so that two
+      // squared magnitudes cost one v_pk_mul_f32 + one v_pk_fma_f32 (norm2's two roundings each) instead of two v_mul_f32 + two
+      // v_fmac_f32; m[k] is still lag t + 256 k (a renaming).  The sum over k stays the sequential chain, and the wave reductions
+      // combine the four rows on DPP too.  Every value is the same bits as with the (re, im) epilogue it replaced.  23 VALU
+      // instructions a row less (439 -> 416, SQ_INSTS_VALU agrees); headline step 1.012 x in the medians, every run above every run of the loop before it on two
+      // boxes (profiles/r15_fused4k_epilogue_ab.log).
+      v2 pl[kR];
+      fft4096<true, true, true>(v, lds, wa, wb, s_tw2 + (t & 15), &pwa, &pl);
+#pragma unroll
+      for (int k = 0; k < kR / 2; k++) {
+        const v2 q = norm2_planar(pl[k], pl[k + kR / 2]);
+        m[k] = __builtin_amdgcn_sqrtf(q.x);                           // np.absolute(ifft(...)) * N
+        m[k + kR / 2] = __builtin_amdgcn_sqrtf(q.y);
+      }
+      float sum_f = m[0];
+#pragma unroll
+      for (int k = 1; k < kR; k++) sum_f += m[k];
+      float wmaxf;
+      unsigned widx;
+      wave_first_max<kR, wave_max_u32_bcast>(m, (unsigned)__builtin_amdgcn_readfirstlane(t & ~63), 1u, 256u, tie_scale, wmaxf, widx);
+      const float wsum = wave_add_f32_bcast(sum_f * inv_n);
+      const unsigned wmax = __builtin_bit_cast(unsigned, wmaxf * inv_n);
+      const int slot = (p - p0) & (kRing - 1);
+      if ((t & 63) == 0) { s_rpeak[slot][t >> 6] = __builtin_bit_cast(float, wmax); s_ridx[slot][t >> 6] = (int)widx; s_rsum[slot][t >> 6] = wsum; }
+      lds_barrier();     // also orders this item's exchange-2 reads before the next item's exchange-1 writes
+      if ((slot == kRing - 1 || p == p1 - 1) && t <= slot) {
+        RowRec r;
+        combine_tagged(kBlock / 64, [&](int w) { return s_rpeak[t][w]; }, [&](int w) { return s_ridx[t][w]; }, tie_scale, r.peak, r.idx);
+        r.sum = (((double)s_rsum[t][0] + (double)s_rsum[t][1]) + (double)s_rsum[t][2]) + (double)s_rsum[t][3];
+        rows[(e * P + (p - slot + t)) * (long)D + d] = r;
+      }
+    }
+    if (map.claim) {
+      const unsigned q = (unsigned)__builtin_amdgcn_readfirstlane((int)s_claim[0]), w = (unsigned)__builtin_amdgcn_readfirstlane((int)s_claim[1]);
+      if (q >= 8) break;
+      pos = f4k_item(map, q, w);
+    } else {
+      f4k_next(map, pos);
+      if (pos.left <= 0) break;
     }
   }
+  F4K_STAMP(2);
 }
 
 int twiddle_table(gacq_ctx* ctx, const float2** out) { return twiddle_cache(ctx, "W4096", kLdsN, kLdsN, out); }
@@ -578,13 +789,56 @@ int lds_fused4k_search(gacq_ctx* ctx, const float2* x, size_t nsamp, int nepoch,
   if (ctx->opt[GACQ_OPT_LDS_PCH] >= 1) pch = (int)ctx->opt[GACQ_OPT_LDS_PCH];
   pch = std::min(pch, nitems);
   const int nchunk = (nitems + pch - 1) / pch;
-  const int by_epoch = nepoch >= 64 ? 1 : 0;
-  const long units8 = by_epoch ? (long)((nepoch + 7) / 8) * D : (units + 7) / 8;      // units per XCD
-  const dim3 grid((unsigned)(8 * units8 * nchunk));
-  hipLaunchKernelGGL(lds_fused4k_kernel, grid, dim3(kBlock), 0, ctx->stream, x, nsamp, spectra, d_items, d_freq, tab, tw, rows,
-                     nepoch, nitems, D, pch, nchunk, by_epoch, tie_scale);
+  if (ctx->cu_count <= 0) {
+    int cus = 0;
+    ctx->cu_count = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && cus > 0 ? cus : 256;
+  }
+  F4kMap map = f4k_map(nepoch, D, nchunk, (int)ctx->opt[GACQ_OPT_F4K_RUN], ctx->cu_count);
+  unsigned* cnt = nullptr;
+  if (f4k_claim_grid(map, ctx->opt[GACQ_OPT_F4K_CLAIM], ctx->cu_count)) {
+    if ((rc = ensure(ctx, ctx->f4k_cnt, sizeof(unsigned) * 8 * kF4kCntPitch)) != GACQ_OK) return rc;
+    cnt = (unsigned*)ctx->f4k_cnt.p;
+    GACQ_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)cnt, (int)(map.grid / 8), 8 * kF4kCntPitch, ctx->stream));      // items 0 .. grid / 8 - 1 of a queue are its workgroups' first ones
+  }
+  hipLaunchKernelGGL(lds_fused4k_kernel, dim3(map.grid), dim3(kBlock), 0, ctx->stream, x, nsamp, spectra, d_items, d_freq, tab, tw, rows,
+                     map, nitems, pch, tie_scale, cnt);
   GACQ_HIP(ctx, hipGetLastError());
   return GACQ_OK;
+}
+
+#ifdef GACQ_F4K_STAMPS
+extern "C" int gacq_debug_f4k_stamps(void* d_stamps, unsigned nblocks) {
+  unsigned long long* p = (unsigned long long*)d_stamps;
+  if (hipMemcpyToSymbol(HIP_SYMBOL(g_f4k_stamps), &p, sizeof(p)) != hipSuccess || hipMemcpyToSymbol(HIP_SYMBOL(g_f4k_nstamps), &nblocks, sizeof(nblocks)) != hipSuccess)
+    return GACQ_ERR_HIP;
+  return GACQ_OK;
+}
+#endif
+
+// test hook (gacq_debug_f4k_map with run < 0): the queues of claimed work, every queue walked in its order
+long lds_debug_f4k_queues(int nepoch, int D, int nchunk, long claim, int cus, int* info, int* work, long cap) {
+  F4kMap map = f4k_map(nepoch, D, nchunk, 1, cus);
+  const bool on = f4k_claim_grid(map, claim, cus);
+  if (info) { info[0] = on ? 1 : 0; info[1] = map.by_epoch; info[2] = 0; info[3] = (int)map.grid; }
+  long n = 0;
+  for (unsigned q = 0; q < 8; q++)
+    for (unsigned w = 0; w < f4k_queue_len(map, q); w++, n++) {
+      const F4kPos pos = f4k_item(map, q, w);
+      if (work && n < cap) { work[4 * n] = (int)q; work[4 * n + 1] = (int)pos.e; work[4 * n + 2] = (int)pos.d; work[4 * n + 3] = (int)pos.c; }
+    }
+  return n;
+}
+
+// test hook (gacq_debug_f4k_map): the walk of every workgroup of the grid a search of this shape would launch, on the host, with the
+// functions the kernel walks with
+long lds_debug_f4k_map(int nepoch, int D, int nchunk, int run, int cus, int* info, int* work, long cap) {
+  const F4kMap map = f4k_map(nepoch, D, nchunk, run, cus);
+  if (info) { info[0] = map.run; info[1] = map.by_epoch; info[2] = map.nruns; info[3] = (int)map.grid; }
+  long n = 0;
+  for (unsigned b = 0; b < map.grid; b++)
+    for (F4kPos pos = f4k_first(map, b); pos.left > 0; f4k_next(map, pos), n++)
+      if (work && n < cap) { work[4 * n] = (int)b; work[4 * n + 1] = (int)pos.e; work[4 * n + 2] = (int)pos.d; work[4 * n + 3] = (int)pos.c; }
+  return n;
 }
 
 int lds_debug_nco(gacq_ctx* ctx, int n, const double* d_freq, int* d_idx) {

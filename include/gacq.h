@@ -169,7 +169,18 @@ int gacq_set_workspace_limit(gacq_ctx* ctx, size_t bytes);
                                 /*     matrix pipe (v_mfma_f32_16x16x4_f32, exact fp32) instead of packed math on the VALU.  Off: measured     */
                                 /*     12-18 % slower -- the stage is paced by its load stream, not by arithmetic                             */
                                 /*     (profiles/r05_engine3_prime_factor_vs_cooley_tukey_ab.log)                                             */
-#define GACQ_NOPTS 18
+#define GACQ_OPT_F4K_RUN 18        /* [1] takes effect only where claimed work (GACQ_OPT_F4K_CLAIM) is off or not engaged -- with the defaults a    */
+                                /*     batch large enough for claimed work ignores it, so a sweep of it sets GACQ_OPT_F4K_CLAIM = 0 too.     */
+                                /*     Fused N = 4096 kernel, static map: consecutive work items (epoch, Doppler bin, item chunk) one       */
+                                /*     workgroup walks, paying its set-up once; 1 = one work item per workgroup; 0 = the fewest runs that   */
+                                /*     leave four rounds of resident workgroups (16 per compute unit); always capped at the work items of   */
+                                /*     one epoch.  Runs longer than 1 measured slower (profiles/r17_fused4k_unit_runs_ab.log): what they save in    */
+                                /*     set-up they lose at the end of the launch, where slots wait for the slowest                          */
+#define GACQ_OPT_F4K_CLAIM 19      /* [1] fused N = 4096 kernel: 1 = claimed work when there is more work than resident workgroups: one workgroup  */
+                                /*     per resident slot (4 per compute unit) stays for the whole launch and takes work items from eight    */
+                                /*     queues (one per XCD, atomic counters), from another XCD's queue when its own is empty; 0 = the static */
+                                /*     map of GACQ_OPT_F4K_RUN; n > 1 = claimed work with n workgroups whatever the shape (tests, sweeps)    */
+#define GACQ_NOPTS 20
 int gacq_set_option(gacq_ctx* ctx, int option, long value);
 int gacq_get_option(gacq_ctx* ctx, int option, long* value);
 
@@ -1002,6 +1013,23 @@ int gacq_debug_row(gacq_sig* sig, const float* x_iq, size_t nsamp, int item, dou
  * kernel: 1 mix_nco_kernel (rocFFT pipeline), 2 lds_forward_kernel / lds16k_forward_kernel, 3 split_outer_forward_kernel,
  *         4 lds16k_fused_kernel, 5 pfa_outer_forward_kernel.  GACQ_ERR_UNSUPPORTED when that kernel does not serve the signal's N. */
 int gacq_debug_nco_indices(gacq_sig* sig, int kernel, double doppler, double bias_hz, int* idx_out);
+
+/* Test hook for "a kernel left a row record undone".  The engines' correlate kernels write one 16-byte record per (epoch, item, bin)
+ * into a buffer that lives as long as the context, so a kernel that skips a record leaves whatever the search before it wrote --
+ * often the right bytes.  This call overwrites every record of that buffer with one that wins any Doppler scan (peak 1e30, lag 1234,
+ * sum 1) and returns how many it wrote (0 before the first search).  row_after >= 0 also arms the next search, once, to overwrite
+ * record row_after (index (epoch x items + item) x bins + bin) the same way between its correlate kernels and its Doppler scan:
+ * what the results of a search look like when exactly that record was skipped.  -1: nothing armed.  Negative return: error. */
+long gacq_debug_poison_rows(gacq_ctx* ctx, long row_after);
+
+/* The block-to-work map of the fused N = 4096 kernel, walked ON THE HOST with the functions the kernel walks with (no device needed):
+ * every workgroup of the grid a search of nepoch epochs x nbins Doppler bins x nchunk item chunks would launch with GACQ_OPT_F4K_RUN =
+ * run on a device of `cus` compute units, in block order, each workgroup's work items in the order it walks them.
+ * info[4] = (resolved run, 1 if the by-epoch map is used, runs per epoch or per XCD, grid size); work[4 i] = (block, epoch, bin, chunk)
+ * of the i-th visit, for i < cap.  Returns the number of visits (it may exceed cap), negative on a bad argument.
+ * run = -c walks the queues of claimed work (GACQ_OPT_F4K_CLAIM = c) instead: info[4] = (1 if claimed work would be used, by-epoch,
+ * 0, grid size), work[4 i] = (queue, epoch, bin, chunk), queue after queue in the order the items are handed out. */
+long gacq_debug_f4k_map(int nepoch, int nbins, int nchunk, int run, int cus, int* info, int* work, long cap);
 
 /* Number of rocFFT plans the context has created so far (a plan for a new length costs 0.5-2 s per process: runtime-compiled kernels).
  * The default engines create none -- code spectra included -- for every FFT length of the reference's scripts; the rocFFT pipeline
