@@ -918,6 +918,63 @@ int gacq_null_run_dev(gacq_null* h, const void* const* d_in, long long in_first,
 void gacq_null_close(gacq_null* h);
 
 /* ---------------------------------------------------------------------------------------------
+ * Space-time adaptive nulling (gacq_stap.hip): gacq_null with T taps on every antenna.  The weight vector has N = M T entries, so
+ * narrowband interferers are separated in frequency as well as in direction; with M = 1 it is an adaptive FIR notch.  Every decision is
+ * a function of the absolute block index, so the bytes do not depend on how the recording is cut into calls.
+ * Input.  antennas = M in 1..8; taps = T, odd, in 1..15; N = M T <= 56 (the int32 apply stays below 2^31: 112 * 131071 * 128 = 1.879e9).
+ *    t_c = (T - 1) / 2.  x_p(j), p < M: interleaved int8 I/Q as stored (-128 is a legal value); x_p(i) = 0 for i < 0.  d_in is a host
+ *    array of M device pointers, each at any byte address; two antennas may share a pointer.
+ * Stacked sample.  Element e = p T + t (antenna-major), t < T:  z_e(j) = x_p(j + t_c - t).  The reference element is e_ref = t_c,
+ *    z_(t_c)(j) = x_0(j): the output keeps the recording's sample index.
+ * 1. Block covariance.  block = Lb, window = W, load_shift as in gacq_null_cfg.  C_b[e][f] = sum z_e(j) conj(z_f(j)) over the samples j
+ *    of block b: the exact sum of the stacked vectors (no Toeplitz approximation; the taps reach t_c samples into the neighbouring
+ *    blocks), formed through the Gram matrix of the 2N real rows as in gacq_null (|G| <= 2^29, every component fits int32).
+ * 2.-5. Window, loading, weights, quantised weights.  Steps 2 to 5 of gacq_null with M replaced by N: R_b in int64, d = (trace R_b >>
+ *    load_shift) + 1, A u = c by the same elimination without pivoting and back substitution in the same written-out order, every real
+ *    product and sum rounded on its own, den summed left to right over all N entries, wq = clamp(rint(w 2^14), +-131071).  The
+ *    elimination updates the whole trailing submatrix (q and r from k + 1 to N - 1): in fp64 the trailing matrix is not exactly
+ *    Hermitian, so the lower triangle is computed, not mirrored.  The constraint c of the N-vector: the M complex entries of the
+ *    configuration on the centre taps, c_(p T + t_c) = (c[2p], c[2p+1]), every other entry zero; the default (1, 0, ..) is power
+ *    inversion with x_0(j) at gain exactly 1.
+ * 6. Apply.  y(j) = sum_e conj(wq_e(j div Lb)) z_e(j) in int32, with the weights of j's own block; the taps reach across block edges
+ *    into the neighbours' samples.
+ * 7., 8. Output and side outputs as gacq_null: complex64 or int8 clip(rint(.), -127, 127); d_stats; d_weights int32 [owned block][N][2];
+ *    d_cov int64 [owned block][N][N][2].
+ * Support.  Output j in block b needs x_p(max(j - t_c, 0) .. j + t_c) and blocks max(b - W, 0) .. max(b, W) - 1 with t_c samples either
+ *    side (samples below 0 do not exist and are not needed): outputs out_first .. out_first + n_out - 1 need inputs
+ *    max(max(out_first div Lb - W, 0) Lb - t_c, 0) .. max(out_first + n_out, W Lb) - 1 + t_c.  A recording of n samples supports outputs
+ *    0 .. n - 1 - t_c, and none until n >= W Lb + t_c.  One that is needed and not present GACQ_ERR_SHORT_INPUT.  Nothing outside
+ *    in_first .. in_first + in_count - 1 of any antenna is read.
+ * The checks, their order, "a refused call leaves every output untouched", n_out = 0, the 2^48 limits and the alignment rules of the
+ * side outputs are those of gacq_null; taps even or outside 1..15 and M T > 56 GACQ_ERR_BAD_ARG, checked after the antennas and
+ * before the block.  With M >= 2 and T = 1 every byte, weight, window sum and count equals gacq_null_run_dev's.
+ * gacq_stap_check makes every check that needs no device pointer, without a context.  gacq_stap_open allocates the handle's workspace,
+ * gacq_stap_workspace bytes: ((K + W) N^2 + K N) * 8 with K = min(2^14, (2^26 - 8 W N^2) div (8 N^2 + 8 N)) blocks per triple of
+ * launches, at most 64 MiB.  gacq_stap_run_dev is three launches (block covariances, weights, outputs) per K blocks on the ctx stream,
+ * asynchronous, without state between calls and without host synchronisation.  The handle is closed before its context is destroyed.
+ * gacq_stap_tile: the output samples one workgroup owns (tiles begin at absolute sample indices that are multiples of it, a lane's run
+ * of 8 samples at multiples of 8), or GACQ_ERR_BAD_ARG.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gacq_stap_cfg {
+  int antennas;                    /* M, 1..8 */
+  int taps;                        /* T, odd, 1..15; M T <= 56 */
+  int block;                       /* Lb: samples per covariance block, a multiple of 64 in 64..32768 */
+  int window;                      /* W: blocks the covariance sums over, 1..64 */
+  int load_shift;                  /* diagonal loading d = (trace >> load_shift) + 1, 0..40 */
+  double c[16];                    /* the constraint: re, im of c_0 .. c_(M-1), on the centre taps; the rest is ignored */
+} gacq_stap_cfg;
+typedef struct gacq_stap gacq_stap;
+
+int gacq_stap_tile(const gacq_stap_cfg* cfg);
+long long gacq_stap_workspace(const gacq_stap_cfg* cfg);
+int gacq_stap_check(const gacq_stap_cfg* cfg, long long in_first, long long in_count, long long out_first, long long n_out, double gain,
+                    int out_complex64);
+int gacq_stap_open(gacq_ctx* ctx, const gacq_stap_cfg* cfg, gacq_stap** out);
+int gacq_stap_run_dev(gacq_stap* h, const void* const* d_in, long long in_first, long long in_count, long long out_first, long long n_out,
+                      double gain, int out_complex64, void* d_out, void* d_stats, void* d_weights, void* d_cov);
+void gacq_stap_close(gacq_stap* h);
+
+/* ---------------------------------------------------------------------------------------------
  * Navigation data from tracked prompts (gacq_navbits.hip; the framing is host code, gnss_dsp_tools_amd/navdata.py).
  *
  * gacq_navsym: symbol forming and bit synchronisation of K channels, one workgroup per channel.  Everything is host memory: the call
