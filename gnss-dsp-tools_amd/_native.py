@@ -204,6 +204,13 @@ SYMBOLS = {
     # synthetic recordings (simulate.py): the gacq_sim_sat array
     "gacq_simulate_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_ulonglong,
                                          ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]),
+    # array-and-interference scenes (scene.py): the gacq_sim_sat and gacq_scene_emitter arrays, the gains, the host array of device pointers
+    "gacq_scene_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double,
+                                        ctypes.c_double, ctypes.c_longlong, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int,
+                                        ctypes.c_void_p]),
+    "gacq_scene_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                      ctypes.c_double, ctypes.c_double, ctypes.c_ulonglong, ctypes.c_longlong, ctypes.c_int, ctypes.c_longlong,
+                                      ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]),
     # recording ingest (ingest.py): the gacq_ingest_fmt
     "gacq_ingest_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                        ctypes.c_longlong, ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),

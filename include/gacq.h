@@ -604,6 +604,60 @@ int gacq_simulate_dev(gacq_ctx* ctx, const gacq_sim_sat* sats, int K, double fs,
                       long long n, int out_complex64, void* d_out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Array-and-interference scenes (gacq_scene.hip): samples j = j0 .. j0 + n - 1 of antennas a = first_antenna .. first_antenna + M - 1
+ * of one endless multi-antenna recording, an exact function of (scene, seed, antenna, absolute sample index) -- the same bytes however
+ * a caller cuts it into calls or into groups of antennas:
+ *     v_a(j) = noise_a(j) + sum_{e < K + I} G[a][e] z_e(j),     noise first, then e ascending, in fp32: the K satellites, then the I
+ *     emitters; per source  vr = fma(-Gi, zi, fma(Gr, zr, vr)),  vi = fma(Gi, zr, fma(Gr, zi, vi)).
+ * Satellites, e < K: z_e(j) is the term amp w d exp(2 pi i theta / 2^64) of gacq_simulate_dev, from the same gacq_sim_sat by the same
+ *     conversions, rounded to fp32 per component.  K = 0..32.
+ * Antenna noise: gacq_simulate_dev's Box-Muller of Philox4x32-10, key = seed, counter (j lo32, j hi32, a, 0): antenna 0 has the
+ *     stream of gacq_simulate_dev.  sigma is per component and the same for every antenna.
+ * Emitters, i = e - K, I = 0..8, one gacq_scene_emitter each:
+ *     gate: on(j) when gate_period = 0, else when ((j - gate_first) mod gate_period) < gate_on (the non-negative modulus), with
+ *       0 <= gate_first < gate_period <= 2^48 and 1 <= gate_on <= gate_period.  z = 0 while the gate is off; the phase runs on.
+ *     kind 0, tone: theta(j) = p0 + j F0 mod 2^64, F0 = floor(frac(f0_hz / fs) 2^64), p0 likewise from phase (turns at j = 0);
+ *       z = amp exp(2 pi i theta / 2^64).
+ *     kind 1 sawtooth chirp, kind 2 triangle chirp: the frequency word steps once per sample, W(u) = F0 + R ramp(u) mod 2^64 at
+ *       u = j mod P (P = sweep), theta(j) = p0 + sum_{t<j} W(t mod P) mod 2^64.  Sawtooth: ramp(u) = u, R = floor((f1_hz - f0_hz) / fs
+ *       / P 2^64).  Triangle: P even, H = P / 2, ramp(u) = u below H and P - 1 - u from H on, R = floor((f1_hz - f0_hz) / fs / H 2^64).
+ *       R is a signed integer taken mod 2^64 (the two divisions in fp64, in that order; the scaling is exact).  Closed form:
+ *       theta = p0 + s Phi + u F0 + R T(u), s = j div P, Phi = P F0 + R T(P), T(u) = u (u - 1) / 2 on the rising ramp (u <= H; the whole
+ *       sawtooth) and H (H - 1) + (u - H)(P - 1) - u (u - 1) / 2 beyond; all products wrap mod 2^64.
+ *     kind 3, broadband noise: Box-Muller of the same Philox with counter (j lo32, j hi32, i, 1) and amp as its sigma per component:
+ *       one waveform common to all antennas, a point source.
+ * gains (host): doubles [M][K + I][2] (re, im), each rounded once to fp32; row p belongs to antenna first_antenna + p.  The narrowband
+ *     array model lives in these numbers only.
+ * d_out (host array of M device pointers): each complex64 [n] (out_complex64 != 0, 8-byte aligned) or interleaved signed 8-bit I/Q
+ *     [2 n] = clip(rint(v), -127, 127), ties to even, of the very values the complex64 form holds, at any address.
+ * gacq_scene_check makes every check that needs no chip generator, before anything is allocated or launched: what gacq_simulate_dev
+ *     refuses except K = 0; M outside 1..8; first_antenna outside 0 .. 2^31 - M; I outside 0..8; kind outside 0..3; a chirp sweep
+ *     outside 2..2^31, an odd triangle sweep, |f1_hz - f0_hz| > fs; gate fields outside the ranges above; a value that is not finite (a
+ *     gain: in fp32); a NULL pointer (sats with K = 0, emitters with I = 0 and gains with K + I = 0 may be NULL); a complex64 row that
+ *     is not 8-byte aligned: GACQ_ERR_BAD_ARG, an unknown code GACQ_ERR_UNKNOWN_CODE; the message is gacq_last_error(NULL).
+ *     gacq_scene_dev makes the same checks and reports an unknown PRN (GACQ_ERR_BAD_PRN) before it allocates or launches anything.
+ *     Outputs are untouched after a refusal.  One launch on the ctx stream, no state kept; asynchronous.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gacq_scene_emitter {
+  int kind;                        /* 0 tone, 1 sawtooth chirp, 2 triangle chirp, 3 broadband noise */
+  int pad;
+  double amp;                      /* amplitude per component, LSB; kind 3: sigma per component */
+  double f0_hz;                    /* frequency in the recording, Hz (chirps: at the start of a sweep); unused by kind 3 */
+  double f1_hz;                    /* chirps: the frequency the ramp ends at */
+  double phase;                    /* phase at j = 0, turns */
+  long long sweep;                 /* chirps: P, samples per sweep */
+  long long gate_period;           /* 0: always on */
+  long long gate_on;               /* samples on per period */
+  long long gate_first;            /* first sample of an on-interval */
+} gacq_scene_emitter;
+
+int gacq_scene_check(const gacq_sim_sat* sats, int K, const gacq_scene_emitter* emitters, int I, const double* gains, double fs, double sigma,
+                     long long first_antenna, int M, long long j0, long long n, int out_complex64, void* const* d_out);
+int gacq_scene_dev(gacq_ctx* ctx, const gacq_sim_sat* sats, int K, const gacq_scene_emitter* emitters, int I, const double* gains, double fs,
+                   double sigma, unsigned long long seed, long long first_antenna, int M, long long j0, long long n, int out_complex64,
+                   void* const* d_out);
+
+/* ---------------------------------------------------------------------------------------------
  * Recording ingest (gacq_ingest.hip): packed, 8-bit, 16-bit and float32 recordings, I/Q or real IF, to the interleaved signed 8-bit
  * I/Q (or complex64) that every other entry point takes.  Output sample m is an exact function of (format, gain, absolute sample
  * index m) -- the same bytes however a caller cuts the recording into calls.
