@@ -22,38 +22,19 @@
 //      lanes of a wave read the same 64 bytes).
 #pragma clang fp contract(off)
 
-#include "gacq_common.h"
+#include "gacq_arraycore.h"
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 
 using namespace gacq;
 
 namespace {
 
-constexpr int kNlBlock = 256;
-constexpr int kNlMaxM = 8, kNlMaxWindow = 64, kNlMaxLb = 32768, kNlMaxShift = 40;
-constexpr long long kNlChunkBlocks = 1ll << 14;      // blocks whose outputs one triple of launches writes, at most (2^29 samples)
-constexpr int kNlRuns = 8;                           // runs a lane works through
-constexpr int kNlTile = kNlBlock * kNlRuns * 8;      // 16384 samples a workgroup
-constexpr unsigned kNlMaxGrid = 1u << 16;            // workgroups; a longer call loops
-constexpr int kNlWq = 1 << 14;                       // weight scale 2^14
-constexpr int kNlWqMax = 131071;
-
-typedef int nl_v4i __attribute__((ext_vector_type(4)));
-
-// 16 bytes at any address: a byte-aligned copy, for which the compiler emits one wide load
-__device__ __forceinline__ uint4 nl_load16(const uint8_t* p) {
-  uint4 v;
-  __builtin_memcpy(&v, p, 16);
-  return v;
-}
-
 // ---- block covariances
 
 struct NlCovArgs {
-  const uint8_t* in[kNlMaxM];   // antenna p: the address of the first sample of block 0 of the launch
+  const uint8_t* in[kArMaxM];   // antenna p: the address of the first sample of block 0 of the launch
   int* C;                       // [block][8][8][2]
   long long nblk;
   int Lb, M;
@@ -62,29 +43,29 @@ struct NlCovArgs {
 
 // two workgroups a compute unit at the least: with at most 256 registers a wave the compiler keeps the matrix instruction's
 // accumulator in VGPRs (with all 512 in reach it takes accumulator registers)
-__global__ __launch_bounds__(kNlBlock, 2) void null_cov_kernel(const NlCovArgs a) {
-  __shared__ int red[kNlBlock / 64][4][64];
+__global__ __launch_bounds__(kArBlock, 2) void null_cov_kernel(const NlCovArgs a) {
+  __shared__ int red[kArBlock / 64][4][64];
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int row = lane & 15, kg = lane >> 4, p = row >> 1;
-  const unsigned sel = (row & 1) ? 0x07050301u : 0x06040200u;           // bytes 1, 3 (Q) or 0, 2 (I) of two dwords
+  const unsigned sel = (row & 1) ? kArSelQ : kArSelI;
   const uint8_t* src = a.in[0];
 #pragma unroll
-  for (int q = 1; q < kNlMaxM; q++)
+  for (int q = 1; q < kArMaxM; q++)
     if (p == q && q < a.M) src = a.in[q];
   const bool live = p < a.M;
-  const int wpb = 1 << a.wpb_log2, per = (kNlBlock / 64) >> a.wpb_log2;
+  const int wpb = 1 << a.wpb_log2, per = (kArBlock / 64) >> a.wpb_log2;
   const int blw = wave >> a.wpb_log2, sub = wave & (wpb - 1);
   const int groups = a.Lb >> 6;
   const long long npass = (a.nblk + per - 1) / per;
   for (long long pass = blockIdx.x; pass < npass; pass += gridDim.x) {
     const long long bl = pass * per + blw;
-    nl_v4i acc = {0, 0, 0, 0};
+    ar_v4i acc = {0, 0, 0, 0};
     if (bl < a.nblk) {
       const uint8_t* pb = src + (bl * a.Lb + 16 * kg) * 2;
       for (int g = sub; g < groups; g += wpb) {
-        nl_v4i f = {0, 0, 0, 0};
+        ar_v4i f = {0, 0, 0, 0};
         if (live) {
-          const uint4 lo = nl_load16(pb + 128 * (long long)g), hi = nl_load16(pb + 128 * (long long)g + 16);
+          const uint4 lo = ar_load16(pb + 128 * (long long)g), hi = ar_load16(pb + 128 * (long long)g + 16);
           f.x = (int)__builtin_amdgcn_perm(lo.y, lo.x, sel);
           f.y = (int)__builtin_amdgcn_perm(lo.w, lo.z, sel);
           f.z = (int)__builtin_amdgcn_perm(hi.y, hi.x, sel);
@@ -127,7 +108,7 @@ struct NlWgtArgs {
   int* Wq;                      // [block][8][2]: the launch's block i at Wq[16 i]
   long long* cov;               // d_cov, or NULL
   int* wout;                    // d_weights, or NULL
-  double c[2 * kNlMaxM];
+  double c[2 * kArMaxM];
   long long b_first;            // the absolute index of the launch's block 0
   long long own_first;          // the call's first owned block
   int nblk;
@@ -136,15 +117,9 @@ struct NlWgtArgs {
   int W, M, shift;
 };
 
-__device__ __forceinline__ int nl_quantise(double w) {
-  const double s = w * (double)kNlWq;
-  if (!__builtin_isfinite(s)) return 0;
-  return (int)fmin(fmax(rint(s), -(double)kNlWqMax), (double)kNlWqMax);
-}
-
-__global__ __launch_bounds__(kNlBlock) void null_weights_kernel(const NlWgtArgs a) {
+__global__ __launch_bounds__(kArBlock) void null_weights_kernel(const NlWgtArgs a) {
   const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * (kNlBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int i = blockIdx.x * (kArBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (i >= a.nblk) return;
   const int r = lane >> 3, c = lane & 7, M = a.M;
   const bool in = r < M && c < M;
@@ -170,7 +145,7 @@ __global__ __launch_bounds__(kNlBlock) void null_weights_kernel(const NlWgtArgs 
   double Are = in ? (double)(Rre + (r == c ? d : 0)) : 0.0, Aim = in ? (double)Rim : 0.0;
   double cre = 0.0, cim = 0.0, bre = 0.0, bim = 0.0;                    // c of the lane's column, b of its row
 #pragma unroll
-  for (int q = 0; q < kNlMaxM; q++) {
+  for (int q = 0; q < kArMaxM; q++) {
     if (c == q && q < M) cre = a.c[2 * q], cim = a.c[2 * q + 1];
     if (r == q && q < M) bre = a.c[2 * q], bim = a.c[2 * q + 1];
   }
@@ -207,7 +182,7 @@ __global__ __launch_bounds__(kNlBlock) void null_weights_kernel(const NlWgtArgs 
   const double tp = cre * ucr + cim * uci;
   double den = __shfl(tp, 0, 64);
   for (int p = 1; p < M; p++) den = den + __shfl(tp, p, 64);
-  const int qr = c < M ? nl_quantise(ucr / den) : 0, qi = c < M ? nl_quantise(uci / den) : 0;
+  const int qr = c < M ? ar_quantise(ucr / den) : 0, qi = c < M ? ar_quantise(uci / den) : 0;
   if (r == 0) {
     *reinterpret_cast<int2*>(a.Wq + 16 * (long long)i + 2 * c) = make_int2(qr, qi);
     if (owned && a.wout && c < M) {
@@ -221,7 +196,7 @@ __global__ __launch_bounds__(kNlBlock) void null_weights_kernel(const NlWgtArgs 
 // ---- outputs
 
 struct NlApplyArgs {
-  const uint8_t* in[kNlMaxM];   // antenna p: the address of input sample j0
+  const uint8_t* in[kArMaxM];   // antenna p: the address of input sample j0
   uint8_t* out;                 // the address of output sample j0
   const int* Wq;                // the weights of block b_first + i at Wq[16 i]
   unsigned long long* stats;
@@ -233,15 +208,15 @@ struct NlApplyArgs {
 };
 
 template <bool F32>
-__global__ __launch_bounds__(kNlBlock) void null_apply_kernel(const NlApplyArgs a) {
+__global__ __launch_bounds__(kArBlock) void null_apply_kernel(const NlApplyArgs a) {
   const int tid = threadIdx.x;
-  const long long t0 = a.j0 / kNlTile, j_end = a.j0 + a.n;
-  const long long ntiles = (j_end - 1) / kNlTile - t0 + 1;
+  const long long t0 = a.j0 / kArTile, j_end = a.j0 + a.n;
+  const long long ntiles = (j_end - 1) / kArTile - t0 + 1;
   unsigned nclip = 0;
   for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
 #pragma unroll 1
-    for (int rr = 0; rr < kNlRuns; rr++) {
-      const long long j = (t0 + tile) * kNlTile + (rr * kNlBlock + tid) * 8;
+    for (int rr = 0; rr < kArRuns; rr++) {
+      const long long j = (t0 + tile) * kArTile + (rr * kArBlock + tid) * 8;
       if (j + 8 <= a.j0 || j >= j_end) continue;
       const bool full = j >= a.j0 && j + 8 <= j_end;
       const int* w = a.Wq + 16 * (long long)((unsigned)(j - a.blk0) / (unsigned)a.Lb);
@@ -249,7 +224,7 @@ __global__ __launch_bounds__(kNlBlock) void null_apply_kernel(const NlApplyArgs 
 #pragma unroll
       for (int e = 0; e < 8; e++) yr[e] = yi[e] = 0;
 #pragma unroll
-      for (int p = 0; p < kNlMaxM; p++) {
+      for (int p = 0; p < kArMaxM; p++) {
         if (p < a.M) {
           const int2 wq = *reinterpret_cast<const int2*>(w + 2 * p);
           const uint8_t* ps = a.in[p] + (j - a.j0) * 2;
@@ -274,111 +249,36 @@ __global__ __launch_bounds__(kNlBlock) void null_apply_kernel(const NlApplyArgs 
           }
         }
       }
-      if constexpr (F32) {
-        float o[16];
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-          o[2 * e] = (float)yr[e] * a.s;
-          o[2 * e + 1] = (float)yi[e] * a.s;
-        }
-        float* po = reinterpret_cast<float*>(a.out) + (j - a.j0) * 2;
-        if (full) {
-          __builtin_memcpy(reinterpret_cast<uint8_t*>(po), o, 64);      // four 16-byte stores; the output lies on 8 bytes
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; e++)
-            if (j + e >= a.j0 && j + e < j_end) *reinterpret_cast<float2*>(po + 2 * e) = make_float2(o[2 * e], o[2 * e + 1]);
-        }
-      } else {
-        unsigned q[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int e = 0; e < 16; e++) {
-          const float v = (float)((e & 1) ? yi[e >> 1] : yr[e >> 1]) * a.s;     // a sample outside the range is 0 here: it clips nothing
-          const float rv = rintf(v);                                    // half to even
-          const float cv = fminf(fmaxf(rv, -127.0f), 127.0f);
-          nclip += cv != rv ? 1u : 0u;
-          q[e >> 2] |= ((unsigned)(int)cv & 0xffu) << (8 * (e & 3));
-        }
-        uint8_t* po = a.out + (j - a.j0) * 2;
-        if (full) {
-          __builtin_memcpy(po, q, 16);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 16; e++)
-            if (j + (e >> 1) >= a.j0 && j + (e >> 1) < j_end) po[e] = (uint8_t)(q[e >> 2] >> (8 * (e & 3)));
-        }
-      }
+      AR_STORE_RUN(F32, yr, yi, a.s, a.out, full, j, a.j0, j_end, nclip)
     }
   }
-  if (a.stats) {
-    if (!F32) {
-      for (int off = 1; off < 64; off <<= 1) nclip += __shfl_xor(nclip, off, 64);
-      if ((tid & 63) == 0 && nclip) atomicAdd(a.stats, (unsigned long long)nclip);
-    }
-    if (blockIdx.x == 0 && tid == 0 && a.owned) atomicAdd(a.stats + 1, a.owned);
-  }
-}
-
-int check_cfg(const gacq_null_cfg* c) {
-  if (!c) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: NULL argument");
-  if (c->antennas < 2 || c->antennas > kNlMaxM)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: %d antennas: need 2..%d", c->antennas, kNlMaxM);
-  if (c->block < 64 || c->block > kNlMaxLb || c->block % 64)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: the block length %d is no multiple of 64 in 64..%d", c->block, kNlMaxLb);
-  if (c->window < 1 || c->window > kNlMaxWindow)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: the window %d lies outside 1..%d", c->window, kNlMaxWindow);
-  if (c->load_shift < 0 || c->load_shift > kNlMaxShift)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: load_shift %d lies outside 0..%d", c->load_shift, kNlMaxShift);
-  bool any = false;
-  for (int i = 0; i < 2 * c->antennas; i++) {
-    if (!std::isfinite(c->c[i])) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: constraint component %d is not finite", i);
-    any = any || c->c[i] != 0.0;
-  }
-  if (!any) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_null: the constraint is all zero");
-  return GACQ_OK;
+  AR_ADD_STATS(F32, a.stats, nclip, a.owned, tid)
 }
 
 }  // namespace
 
-#include "gacq_streamhost.h"
+#include "gacq_arrayhost.h"
 
-struct gacq_null {
-  gacq_ctx* ctx = nullptr;
-  gacq_null_cfg cfg{};
-  StDevBlock dev;               // the block covariances of a triple of launches, then the weights of its blocks
-};
+struct gacq_null : ArHandle<gacq_null_cfg> {};
+
+static int check_cfg(const gacq_null_cfg* c) {
+  return ar_check_cfg("gacq_null", 2, c, [](const gacq_null_cfg&) { return GACQ_OK; });
+}
 
 extern "C" int gacq_null_tile(const gacq_null_cfg* cfg) {
   if (!cfg || check_cfg(cfg) < 0) return GACQ_ERR_BAD_ARG;
-  return kNlTile;
+  return kArTile;
 }
 
 extern "C" int gacq_null_check(const gacq_null_cfg* cfg, long long in_first, long long in_count, long long out_first, long long n_out, double gain,
                                int out_complex64) {
   (void)out_complex64;                                                  // either form takes every range
-  int rc = check_cfg(cfg);
-  if (rc == GACQ_OK) rc = st_check_gain(nullptr, "gacq_null", "is not finite and positive", gain);
-  if (rc == GACQ_OK) rc = st_check_range(nullptr, "gacq_null", in_first, in_count, out_first, n_out);
-  if (rc < 0 || n_out == 0) return rc;
-  return st_check_block_support(nullptr, "gacq_null", cfg->block, cfg->window, out_first, n_out, in_first, in_count);
+  return ar_check_call("gacq_null", check_cfg(cfg), cfg, 0, in_first, in_count, out_first, n_out, gain);
 }
 
 extern "C" int gacq_null_open(gacq_ctx* ctx, const gacq_null_cfg* cfg, gacq_null** out) {
-  if (!ctx) return GACQ_ERR_BAD_ARG;
-  if (!out) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_open: NULL argument");
-  *out = nullptr;
-  const int rc = gacq_null_check(cfg, 0, 0, 0, 0, 1.0, 0);
-  if (rc < 0) return st_forward(ctx, rc);
-  std::unique_ptr<gacq_null> h(new gacq_null);
-  h->ctx = ctx;
-  h->cfg = *cfg;
-  {
-    GACQ_DEVICE(ctx);
-    const hipError_t e = h->dev.alloc(ctx, ((size_t)(kNlChunkBlocks + kNlMaxWindow) * 128 + (size_t)kNlChunkBlocks * 16) * sizeof(int));
-    if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_null_open: %s", hipGetErrorString(e));
-  }
-  *out = h.release();
-  return GACQ_OK;
+  return ar_open("gacq_null_open", ctx, cfg, out, gacq_null_check,
+                 [](gacq_null&) { return ((size_t)(kArMaxChunk + kArMaxWindow) * 128 + (size_t)kArMaxChunk * 16) * sizeof(int); });
 }
 
 extern "C" void gacq_null_close(gacq_null* h) { delete h; }
@@ -386,75 +286,35 @@ extern "C" void gacq_null_close(gacq_null* h) { delete h; }
 extern "C" int gacq_null_run_dev(gacq_null* h, const void* const* d_in, long long in_first, long long in_count, long long out_first, long long n_out,
                                  double gain, int out_complex64, void* d_out, void* d_stats, void* d_weights, void* d_cov) {
   if (!h) return GACQ_ERR_BAD_ARG;
-  gacq_ctx* ctx = h->ctx;
   const gacq_null_cfg& c = h->cfg;
-  if (!d_in || !d_out) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: NULL argument");
-  for (int p = 0; p < c.antennas; p++)
-    if (!d_in[p]) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: the pointer of antenna %d is NULL", p);
-  // everything is checked before anything is launched
-  int rc = gacq_null_check(&c, in_first, in_count, out_first, n_out, gain, out_complex64);
-  if (rc < 0) return st_forward(ctx, rc);
-  if (out_complex64 && (uintptr_t)d_out % 8u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: complex64 output must be 8-byte aligned");
-  if ((uintptr_t)d_stats % 8u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: d_stats must be 8-byte aligned");
-  if ((uintptr_t)d_weights % 4u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: d_weights must be 4-byte aligned");
-  if ((uintptr_t)d_cov % 8u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_null_run_dev: d_cov must be 8-byte aligned");
-  if (n_out == 0) return GACQ_OK;
-  const int M = c.antennas;
-  const long long Lb = c.block, W = c.window, out_end = out_first + n_out;
-  const long long own_first = (out_first + Lb - 1) / Lb;
-  int* dC = (int*)h->dev.p;
-  int* dWq = dC + (size_t)(kNlChunkBlocks + kNlMaxWindow) * 128;
-  GACQ_DEVICE(ctx);
-  for (long long o = out_first; o < out_end;) {
-    const long long b0 = o / Lb, o_end = std::min(out_end, (b0 + kNlChunkBlocks) * Lb), b_hi = (o_end - 1) / Lb;
-    // ---- the covariances the weights of blocks b0 .. b_hi need
-    NlCovArgs cv;
-    const long long pb0 = std::max(b0 - W, 0ll);
-    for (int p = 0; p < kNlMaxM; p++) cv.in[p] = (const uint8_t*)d_in[p < M ? p : 0] + (pb0 * Lb - in_first) * 2;
-    cv.C = dC;
-    cv.nblk = std::max(b_hi, W) - pb0;
-    cv.Lb = (int)Lb;
-    cv.M = M;
-    cv.wpb_log2 = Lb >= 256 ? 2 : Lb >= 128 ? 1 : 0;
-    const long long per = (kNlBlock / 64) >> cv.wpb_log2, npass = (cv.nblk + per - 1) / per;
-    hipLaunchKernelGGL(null_cov_kernel, dim3((unsigned)std::min<long long>(npass, (long long)kNlMaxGrid)), dim3(kNlBlock), 0, ctx->stream, cv);
-    if ((rc = st_launched(ctx, "gacq_null_run_dev")) < 0) return rc;
-    // ---- the weights of blocks b0 .. b_hi
-    NlWgtArgs wg;
-    wg.C = dC;
-    wg.Wq = dWq;
-    wg.cov = (long long*)d_cov;
-    wg.wout = (int*)d_weights;
-    for (int i = 0; i < 2 * kNlMaxM; i++) wg.c[i] = i < 2 * M ? c.c[i] : 0.0;
-    wg.b_first = b0;
-    wg.own_first = own_first;
-    wg.nblk = (int)(b_hi - b0 + 1);
-    wg.p_off = (int)(b0 - pb0);
-    wg.warm = (int)std::max(W - b0, 0ll);
-    wg.W = (int)W;
-    wg.M = M;
-    wg.shift = c.load_shift;
-    hipLaunchKernelGGL(null_weights_kernel, dim3((unsigned)((wg.nblk + kNlBlock / 64 - 1) / (kNlBlock / 64))), dim3(kNlBlock), 0, ctx->stream, wg);
-    if ((rc = st_launched(ctx, "gacq_null_run_dev")) < 0) return rc;
-    // ---- the outputs o .. o_end - 1
-    NlApplyArgs ap;
-    for (int p = 0; p < kNlMaxM; p++) ap.in[p] = (const uint8_t*)d_in[p < M ? p : 0] + (o - in_first) * 2;
-    ap.out = (uint8_t*)d_out + (o - out_first) * (out_complex64 ? 8 : 2);
-    ap.Wq = dWq;
-    ap.stats = (unsigned long long*)d_stats;
-    ap.j0 = o;
-    ap.n = o_end - o;
-    ap.blk0 = b0 * Lb;
-    ap.owned = (unsigned long long)((o_end + Lb - 1) / Lb - (o + Lb - 1) / Lb);
-    ap.s = (float)gain * (1.0f / (float)kNlWq);
-    ap.Lb = (int)Lb;
-    ap.M = M;
-    const long long ntiles = (o_end - 1) / kNlTile - o / kNlTile + 1;
-    const unsigned grid = (unsigned)std::min<long long>(ntiles, (long long)kNlMaxGrid);
-    if (out_complex64) hipLaunchKernelGGL(null_apply_kernel<true>, dim3(grid), dim3(kNlBlock), 0, ctx->stream, ap);
-    else hipLaunchKernelGGL(null_apply_kernel<false>, dim3(grid), dim3(kNlBlock), 0, ctx->stream, ap);
-    if ((rc = st_launched(ctx, "gacq_null_run_dev")) < 0) return rc;
-    o = o_end;
-  }
-  return GACQ_OK;
+  hipStream_t stream = h->ctx->stream;
+  return ar_run_dev(
+      "gacq_null_run_dev", *h, gacq_null_check, ArRun{d_in, in_first, in_count, out_first, n_out, gain, out_complex64, d_out, d_stats, d_weights, d_cov},
+      kArMaxChunk, (size_t)(kArMaxChunk + kArMaxWindow) * 128,
+      [&](const ArRun& r) {
+        NlCovArgs cv;
+        ar_inputs(cv.in, r, c.antennas, r.pb0 * c.block);
+        cv.C = r.dC;
+        cv.nblk = r.ncov;
+        cv.Lb = c.block;
+        cv.M = c.antennas;
+        cv.wpb_log2 = c.block >= 256 ? 2 : c.block >= 128 ? 1 : 0;
+        const long long per = (kArBlock / 64) >> cv.wpb_log2, npass = (cv.nblk + per - 1) / per;
+        hipLaunchKernelGGL(null_cov_kernel, dim3((unsigned)std::min<long long>(npass, (long long)kArMaxGrid)), dim3(kArBlock), 0, stream, cv);
+      },
+      [&](const ArRun& r) {
+        NlWgtArgs wg;
+        ar_fill_weights(wg, c, r);
+        hipLaunchKernelGGL(null_weights_kernel, dim3((unsigned)((wg.nblk + kArBlock / 64 - 1) / (kArBlock / 64))), dim3(kArBlock), 0, stream, wg);
+      },
+      [&](const ArRun& r) {
+        NlApplyArgs ap;
+        ar_fill_apply(ap, c, r);
+        ap.j0 = r.o;
+        ap.n = r.o_end - r.o;
+        ap.blk0 = r.b0 * c.block;
+        if (r.out_complex64) hipLaunchKernelGGL(null_apply_kernel<true>, dim3(r.grid), dim3(kArBlock), 0, stream, ap);
+        else hipLaunchKernelGGL(null_apply_kernel<false>, dim3(r.grid), dim3(kArBlock), 0, stream, ap);
+      });
 }
+

@@ -24,41 +24,24 @@
 //      multiply-adds a sample, one 16-byte store (int8) or four (complex64).  A workgroup owns the 16384 samples at a multiple of 16384.
 #pragma clang fp contract(off)
 
-#include "gacq_common.h"
+#include "gacq_arraycore.h"
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 
 using namespace gacq;
 
 namespace {
 
-constexpr int kStBlock = 256;
-constexpr int kStMaxM = 8, kStMaxT = 15, kStMaxN = 56, kStMaxWindow = 64, kStMaxLb = 32768, kStMaxShift = 40;
-constexpr long long kStMaxChunk = 1ll << 14;         // blocks whose outputs one triple of launches writes, at most
+constexpr int kStMaxT = 15, kStMaxN = 56;
 constexpr size_t kStWorkspace = 64u << 20;           // bytes of the handle's workspace, at most
-constexpr int kStRuns = 8;                           // runs a lane works through
-constexpr int kStTile = kStBlock * kStRuns * 8;      // 16384 samples a workgroup
-constexpr unsigned kStMaxGrid = 1u << 16;            // workgroups; a longer call loops
-constexpr int kStWq = 1 << 14;                       // weight scale 2^14
-constexpr int kStWqMax = 131071;
 constexpr int kStMaxTiles = (2 * kStMaxN + 15) / 16; // 7 tiles of 16 real rows
 constexpr int kStStride = kStMaxN + 1;               // doubles between the rows of a plane in LDS: odd, so rows fall on different banks
-
-typedef int st_v4i __attribute__((ext_vector_type(4)));
-
-// 16 bytes at any address: a byte-aligned copy, for which the compiler emits one wide load
-__device__ __forceinline__ uint4 st_load16(const uint8_t* p) {
-  uint4 v;
-  __builtin_memcpy(&v, p, 16);
-  return v;
-}
 
 // ---- block covariances
 
 struct StCovArgs {
-  const uint8_t* in[kStMaxM];   // antenna p: the address of the first sample of block 0 of the launch
+  const uint8_t* in[kArMaxM];   // antenna p: the address of the first sample of block 0 of the launch
   int* C;                       // [block][N][N][2]
   long long nblk;
   long long abs0;               // the absolute index of that sample
@@ -67,12 +50,12 @@ struct StCovArgs {
 
 // The fragment of a lane's row over 16 samples that begin at absolute sample s (the address p): the I or the Q bytes.  Samples below
 // 0 do not exist: they are zeros, and nothing below the recording's first byte is read.
-__device__ __forceinline__ st_v4i st_fragment(const uint8_t* p, long long s, unsigned sel, bool live) {
-  st_v4i f = {0, 0, 0, 0};
+__device__ __forceinline__ ar_v4i st_fragment(const uint8_t* p, long long s, unsigned sel, bool live) {
+  ar_v4i f = {0, 0, 0, 0};
   if (live) {
     unsigned w[8];
     if (s >= 0) {
-      const uint4 lo = st_load16(p), hi = st_load16(p + 16);
+      const uint4 lo = ar_load16(p), hi = ar_load16(p + 16);
       w[0] = lo.x, w[1] = lo.y, w[2] = lo.z, w[3] = lo.w, w[4] = hi.x, w[5] = hi.y, w[6] = hi.z, w[7] = hi.w;
     } else {
 #pragma unroll
@@ -92,20 +75,20 @@ __device__ __forceinline__ st_v4i st_fragment(const uint8_t* p, long long s, uns
 }
 
 // two workgroups a compute unit at the least, as null_cov_kernel: the accumulators stay in VGPRs
-__global__ __launch_bounds__(kStBlock, 2) void stap_cov_kernel(const StCovArgs a) {
+__global__ __launch_bounds__(kArBlock, 2) void stap_cov_kernel(const StCovArgs a) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int row = lane & 15, kg = lane >> 4, tc = (a.T - 1) >> 1;
-  const unsigned sel = (row & 1) ? 0x07050301u : 0x06040200u;           // bytes 1, 3 (Q) or 0, 2 (I) of two dwords
-  const long long units = a.nblk * a.nt, step = (long long)gridDim.x * (kStBlock / 64);
+  const unsigned sel = (row & 1) ? kArSelQ : kArSelI;
+  const long long units = a.nblk * a.nt, step = (long long)gridDim.x * (kArBlock / 64);
   const int groups = a.Lb >> 6;
-  for (long long unit = (long long)blockIdx.x * (kStBlock / 64) + wave; unit < units; unit += step) {
+  for (long long unit = (long long)blockIdx.x * (kArBlock / 64) + wave; unit < units; unit += step) {
     const long long bl = unit / a.nt;
     const int tu = (int)(unit - bl * a.nt);
     // the lane's row of every tile of the unit: where its samples begin, in the block's coordinates
     const uint8_t* src[kStMaxTiles];
     int shift[kStMaxTiles];
     bool live[kStMaxTiles];
-    st_v4i acc[kStMaxTiles];
+    ar_v4i acc[kStMaxTiles];
 #pragma unroll
     for (int d = 0; d < kStMaxTiles; d++) {
       const int e = 8 * (tu + d) + (row >> 1);
@@ -113,20 +96,20 @@ __global__ __launch_bounds__(kStBlock, 2) void stap_cov_kernel(const StCovArgs a
       const int p = live[d] ? e / a.T : 0, t = live[d] ? e - p * a.T : tc;
       const uint8_t* s = a.in[0];
 #pragma unroll
-      for (int q = 1; q < kStMaxM; q++)
+      for (int q = 1; q < kArMaxM; q++)
         if (p == q) s = a.in[q];
       shift[d] = 16 * kg + tc - t;
       src[d] = s + (bl * a.Lb + shift[d]) * 2;
-      acc[d] = st_v4i{0, 0, 0, 0};
+      acc[d] = ar_v4i{0, 0, 0, 0};
     }
     const long long first = a.abs0 + bl * a.Lb;
     for (int g = 0; g < groups; g++) {
-      const st_v4i fu = st_fragment(src[0] + 128 * (long long)g, first + 64 * g + shift[0], sel, live[0]);
+      const ar_v4i fu = st_fragment(src[0] + 128 * (long long)g, first + 64 * g + shift[0], sel, live[0]);
       acc[0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fu, fu, acc[0], 0, 0, 0);
 #pragma unroll
       for (int d = 1; d < kStMaxTiles; d++) {
         if (tu + d < a.nt) {
-          const st_v4i fv = st_fragment(src[d] + 128 * (long long)g, first + 64 * g + shift[d], sel, live[d]);
+          const ar_v4i fv = st_fragment(src[d] + 128 * (long long)g, first + 64 * g + shift[d], sel, live[d]);
           acc[d] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fu, fv, acc[d], 0, 0, 0);
         }
       }
@@ -164,7 +147,7 @@ struct StWgtArgs {
   int* Wq;                      // [block][N][2]
   long long* cov;               // d_cov, or NULL
   int* wout;                    // d_weights, or NULL
-  double c[2 * kStMaxM];
+  double c[2 * kArMaxM];
   long long b_first;            // the absolute index of the launch's block 0
   long long own_first;          // the call's first owned block
   int nblk;
@@ -173,13 +156,7 @@ struct StWgtArgs {
   int W, M, T, N, shift;
 };
 
-__device__ __forceinline__ int st_quantise(double w) {
-  const double s = w * (double)kStWq;
-  if (!__builtin_isfinite(s)) return 0;
-  return (int)fmin(fmax(rint(s), -(double)kStWqMax), (double)kStWqMax);
-}
-
-__global__ __launch_bounds__(kStBlock) void stap_weights_kernel(const StWgtArgs a) {
+__global__ __launch_bounds__(kArBlock) void stap_weights_kernel(const StWgtArgs a) {
   __shared__ double Are[kStMaxN * kStStride], Aim[kStMaxN * kStStride];
   __shared__ double bre[kStMaxN], bim[kStMaxN], pre[2][kStMaxN], pim[2][kStMaxN];
   const int tid = threadIdx.x, i = blockIdx.x, N = a.N, tc = (a.T - 1) >> 1;
@@ -188,7 +165,7 @@ __global__ __launch_bounds__(kStBlock) void stap_weights_kernel(const StWgtArgs 
   // ---- the window sum
   const long long nn = (long long)N * N;
   const int* pc = a.C + (long long)(i >= a.warm ? a.p_off + i - a.W : 0) * nn * 2;
-  for (int el = tid; el < N * N; el += kStBlock) {
+  for (int el = tid; el < N * N; el += kArBlock) {
     long long Rre = 0, Rim = 0;
     for (int j = 0; j < a.W; j++) {
       const int2 v = *reinterpret_cast<const int2*>(pc + (j * nn + el) * 2);
@@ -210,7 +187,7 @@ __global__ __launch_bounds__(kStBlock) void stap_weights_kernel(const StWgtArgs 
     const int p = tid / a.T;
     if (tid - p * a.T == tc) {
 #pragma unroll
-      for (int q = 0; q < kStMaxM; q++)
+      for (int q = 0; q < kArMaxM; q++)
         if (p == q) cre = a.c[2 * q], cim = a.c[2 * q + 1];
     }
     bre[tid] = cre;
@@ -273,7 +250,7 @@ __global__ __launch_bounds__(kStBlock) void stap_weights_kernel(const StWgtArgs 
   if (tid < N) {
     double den = pre[0][0];
     for (int p = 1; p < N; p++) den = den + pre[0][p];
-    const int qr = st_quantise(ucr / den), qi = st_quantise(uci / den);
+    const int qr = ar_quantise(ucr / den), qi = ar_quantise(uci / den);
     *reinterpret_cast<int2*>(a.Wq + ((long long)i * N + tid) * 2) = make_int2(qr, qi);
     if (owned && a.wout) {
       int* o = a.wout + ((b - a.own_first) * N + tid) * 2;
@@ -287,7 +264,7 @@ __global__ __launch_bounds__(kStBlock) void stap_weights_kernel(const StWgtArgs 
 
 // Sample indices are relative to j0, the launch's first output: a launch covers at most 2^29 samples, so they are 32-bit.
 struct StApplyArgs {
-  const uint8_t* in[kStMaxM];   // antenna p: the address of input sample j0 (it may lie before the input; lo says what is there)
+  const uint8_t* in[kArMaxM];   // antenna p: the address of input sample j0 (it may lie before the input; lo says what is there)
   uint8_t* out;                 // the address of output sample j0
   const int* Wq;                // the weights of block b_first + i at Wq[2 N i]
   unsigned long long* stats;
@@ -301,15 +278,15 @@ struct StApplyArgs {
 };
 
 template <bool F32, int T>
-__global__ __launch_bounds__(kStBlock) void stap_apply_kernel(const StApplyArgs a) {
-  constexpr int TC = (T - 1) / 2, PM = kStMaxN / T < kStMaxM ? kStMaxN / T : kStMaxM;
+__global__ __launch_bounds__(kArBlock) void stap_apply_kernel(const StApplyArgs a) {
+  constexpr int TC = (T - 1) / 2, PM = kStMaxN / T < kArMaxM ? kStMaxN / T : kArMaxM;
   const int tid = threadIdx.x, N = a.M * T;
-  const int ntiles = (a.phase + a.n - 1) / kStTile + 1;
+  const int ntiles = (a.phase + a.n - 1) / kArTile + 1;
   unsigned nclip = 0;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
 #pragma unroll 1
-    for (int rr = 0; rr < kStRuns; rr++) {
-      const int j = tile * kStTile - a.phase + (rr * kStBlock + tid) * 8;
+    for (int rr = 0; rr < kArRuns; rr++) {
+      const int j = tile * kArTile - a.phase + (rr * kArBlock + tid) * 8;
       if (j + 8 <= 0 || j >= a.n) continue;
       const bool full = j >= 0 && j + 8 <= a.n;
       const bool wide = j - 8 >= a.lo && j + 16 <= a.hi;               // samples j - 8 .. j + 15 are all present
@@ -357,108 +334,53 @@ __global__ __launch_bounds__(kStBlock) void stap_apply_kernel(const StApplyArgs 
         for (int e = 0; e < 8; e++)
           if (j + e < 0 || j + e >= a.n) yr[e] = yi[e] = 0;
       }
-      if constexpr (F32) {
-        float o[16];
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-          o[2 * e] = (float)yr[e] * a.s;
-          o[2 * e + 1] = (float)yi[e] * a.s;
-        }
-        float* po = reinterpret_cast<float*>(a.out) + j * 2;
-        if (full) {
-          __builtin_memcpy(reinterpret_cast<uint8_t*>(po), o, 64);      // four 16-byte stores; the output lies on 8 bytes
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; e++)
-            if (j + e >= 0 && j + e < a.n) *reinterpret_cast<float2*>(po + 2 * e) = make_float2(o[2 * e], o[2 * e + 1]);
-        }
-      } else {
-        unsigned q[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int e = 0; e < 16; e++) {
-          const float v = (float)((e & 1) ? yi[e >> 1] : yr[e >> 1]) * a.s;
-          const float rv = rintf(v);                                    // half to even
-          const float cv = fminf(fmaxf(rv, -127.0f), 127.0f);
-          nclip += cv != rv ? 1u : 0u;
-          q[e >> 2] |= ((unsigned)(int)cv & 0xffu) << (8 * (e & 3));
-        }
-        uint8_t* po = a.out + j * 2;
-        if (full) {
-          __builtin_memcpy(po, q, 16);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 16; e++)
-            if (j + (e >> 1) >= 0 && j + (e >> 1) < a.n) po[e] = (uint8_t)(q[e >> 2] >> (8 * (e & 3)));
-        }
-      }
+      AR_STORE_RUN(F32, yr, yi, a.s, a.out, full, j, 0, a.n, nclip)
     }
   }
-  if (a.stats) {
-    if (!F32) {
-      for (int off = 1; off < 64; off <<= 1) nclip += __shfl_xor(nclip, off, 64);
-      if ((tid & 63) == 0 && nclip) atomicAdd(a.stats, (unsigned long long)nclip);
-    }
-    if (blockIdx.x == 0 && tid == 0 && a.owned) atomicAdd(a.stats + 1, a.owned);
-  }
+  AR_ADD_STATS(F32, a.stats, nclip, a.owned, tid)
 }
 
 template <bool F32>
 void launch_apply(int T, unsigned grid, hipStream_t stream, const StApplyArgs& ap) {
   switch (T) {
-    case 1: hipLaunchKernelGGL((stap_apply_kernel<F32, 1>), dim3(grid), dim3(kStBlock), 0, stream, ap); break;
-    case 3: hipLaunchKernelGGL((stap_apply_kernel<F32, 3>), dim3(grid), dim3(kStBlock), 0, stream, ap); break;
-    case 5: hipLaunchKernelGGL((stap_apply_kernel<F32, 5>), dim3(grid), dim3(kStBlock), 0, stream, ap); break;
-    case 7: hipLaunchKernelGGL((stap_apply_kernel<F32, 7>), dim3(grid), dim3(kStBlock), 0, stream, ap); break;
-    case 9: hipLaunchKernelGGL((stap_apply_kernel<F32, 9>), dim3(grid), dim3(kStBlock), 0, stream, ap); break;
-    case 11: hipLaunchKernelGGL((stap_apply_kernel<F32, 11>), dim3(grid), dim3(kStBlock), 0, stream, ap); break;
-    case 13: hipLaunchKernelGGL((stap_apply_kernel<F32, 13>), dim3(grid), dim3(kStBlock), 0, stream, ap); break;
-    default: hipLaunchKernelGGL((stap_apply_kernel<F32, 15>), dim3(grid), dim3(kStBlock), 0, stream, ap); break;
+    case 1: hipLaunchKernelGGL((stap_apply_kernel<F32, 1>), dim3(grid), dim3(kArBlock), 0, stream, ap); break;
+    case 3: hipLaunchKernelGGL((stap_apply_kernel<F32, 3>), dim3(grid), dim3(kArBlock), 0, stream, ap); break;
+    case 5: hipLaunchKernelGGL((stap_apply_kernel<F32, 5>), dim3(grid), dim3(kArBlock), 0, stream, ap); break;
+    case 7: hipLaunchKernelGGL((stap_apply_kernel<F32, 7>), dim3(grid), dim3(kArBlock), 0, stream, ap); break;
+    case 9: hipLaunchKernelGGL((stap_apply_kernel<F32, 9>), dim3(grid), dim3(kArBlock), 0, stream, ap); break;
+    case 11: hipLaunchKernelGGL((stap_apply_kernel<F32, 11>), dim3(grid), dim3(kArBlock), 0, stream, ap); break;
+    case 13: hipLaunchKernelGGL((stap_apply_kernel<F32, 13>), dim3(grid), dim3(kArBlock), 0, stream, ap); break;
+    default: hipLaunchKernelGGL((stap_apply_kernel<F32, 15>), dim3(grid), dim3(kArBlock), 0, stream, ap); break;
   }
-}
-
-int check_cfg(const gacq_stap_cfg* c) {
-  if (!c) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_stap: NULL argument");
-  if (c->antennas < 1 || c->antennas > kStMaxM)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_stap: %d antennas: need 1..%d", c->antennas, kStMaxM);
-  if (c->taps < 1 || c->taps > kStMaxT || c->taps % 2 == 0)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_stap: %d taps: need an odd number in 1..%d", c->taps, kStMaxT);
-  if (c->antennas * c->taps > kStMaxN)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_stap: %d antennas x %d taps: need at most %d weights", c->antennas, c->taps, kStMaxN);
-  if (c->block < 64 || c->block > kStMaxLb || c->block % 64)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_stap: the block length %d is no multiple of 64 in 64..%d", c->block, kStMaxLb);
-  if (c->window < 1 || c->window > kStMaxWindow)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_stap: the window %d lies outside 1..%d", c->window, kStMaxWindow);
-  if (c->load_shift < 0 || c->load_shift > kStMaxShift)
-    return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_stap: load_shift %d lies outside 0..%d", c->load_shift, kStMaxShift);
-  bool any = false;
-  for (int i = 0; i < 2 * c->antennas; i++) {
-    if (!std::isfinite(c->c[i])) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_stap: constraint component %d is not finite", i);
-    any = any || c->c[i] != 0.0;
-  }
-  if (!any) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_stap: the constraint is all zero");
-  return GACQ_OK;
-}
-
-// blocks a triple of launches covers: the covariances of chunk + W blocks and the weights of chunk blocks fit the workspace
-long long chunk_blocks(const gacq_stap_cfg& c) {
-  const size_t N = (size_t)c.antennas * c.taps, cov = N * N * 2 * sizeof(int), wgt = N * 2 * sizeof(int);
-  return std::min<long long>(kStMaxChunk, (long long)((kStWorkspace - (size_t)c.window * cov) / (cov + wgt)));
 }
 
 }  // namespace
 
-#include "gacq_streamhost.h"
+#include "gacq_arrayhost.h"
 
-struct gacq_stap {
-  gacq_ctx* ctx = nullptr;
-  gacq_stap_cfg cfg{};
-  long long chunk = 0;
-  StDevBlock dev;               // the block covariances of a triple of launches, then the weights of its blocks
+struct gacq_stap : ArHandle<gacq_stap_cfg> {
+  long long chunk = 0;          // blocks a triple of launches covers
 };
+
+static int check_cfg(const gacq_stap_cfg* cfg) {
+  return ar_check_cfg("gacq_stap", 1, cfg, [](const gacq_stap_cfg& c) {
+    if (c.taps < 1 || c.taps > kStMaxT || c.taps % 2 == 0)
+      return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_stap: %d taps: need an odd number in 1..%d", c.taps, kStMaxT);
+    if (c.antennas * c.taps > kStMaxN)
+      return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_stap: %d antennas x %d taps: need at most %d weights", c.antennas, c.taps, kStMaxN);
+    return (int)GACQ_OK;
+  });
+}
+
+// blocks a triple of launches covers: the covariances of chunk + W blocks and the weights of chunk blocks fit the workspace
+static long long chunk_blocks(const gacq_stap_cfg& c) {
+  const size_t N = (size_t)c.antennas * c.taps, cov = N * N * 2 * sizeof(int), wgt = N * 2 * sizeof(int);
+  return std::min<long long>(kArMaxChunk, (long long)((kStWorkspace - (size_t)c.window * cov) / (cov + wgt)));
+}
 
 extern "C" int gacq_stap_tile(const gacq_stap_cfg* cfg) {
   if (!cfg || check_cfg(cfg) < 0) return GACQ_ERR_BAD_ARG;
-  return kStTile;
+  return kArTile;
 }
 
 extern "C" long long gacq_stap_workspace(const gacq_stap_cfg* cfg) {
@@ -470,32 +392,14 @@ extern "C" long long gacq_stap_workspace(const gacq_stap_cfg* cfg) {
 extern "C" int gacq_stap_check(const gacq_stap_cfg* cfg, long long in_first, long long in_count, long long out_first, long long n_out, double gain,
                                int out_complex64) {
   (void)out_complex64;                                                  // either form takes every range
-  int rc = check_cfg(cfg);
-  if (rc == GACQ_OK) rc = st_check_gain(nullptr, "gacq_stap", "is not finite and positive", gain);
-  if (rc == GACQ_OK) rc = st_check_range(nullptr, "gacq_stap", in_first, in_count, out_first, n_out);
-  if (rc < 0 || n_out == 0) return rc;
-  const long long Lb = cfg->block, W = cfg->window, tc = (cfg->taps - 1) / 2;
-  return st_check_support(nullptr, "gacq_stap", out_first, n_out, std::max(std::max(out_first / Lb - W, 0ll) * Lb - tc, 0ll),
-                          std::max(out_first + n_out, W * Lb) - 1 + tc, in_first, in_count);
+  return ar_check_call("gacq_stap", check_cfg(cfg), cfg, cfg ? (cfg->taps - 1) / 2 : 0, in_first, in_count, out_first, n_out, gain);
 }
 
 extern "C" int gacq_stap_open(gacq_ctx* ctx, const gacq_stap_cfg* cfg, gacq_stap** out) {
-  if (!ctx) return GACQ_ERR_BAD_ARG;
-  if (!out) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_stap_open: NULL argument");
-  *out = nullptr;
-  const int rc = gacq_stap_check(cfg, 0, 0, 0, 0, 1.0, 0);
-  if (rc < 0) return st_forward(ctx, rc);
-  std::unique_ptr<gacq_stap> h(new gacq_stap);
-  h->ctx = ctx;
-  h->cfg = *cfg;
-  h->chunk = chunk_blocks(*cfg);
-  {
-    GACQ_DEVICE(ctx);
-    const hipError_t e = h->dev.alloc(ctx, (size_t)gacq_stap_workspace(cfg));
-    if (e != hipSuccess) return set_error(ctx, GACQ_ERR_HIP, "gacq_stap_open: %s", hipGetErrorString(e));
-  }
-  *out = h.release();
-  return GACQ_OK;
+  return ar_open("gacq_stap_open", ctx, cfg, out, gacq_stap_check, [](gacq_stap& h) {
+    h.chunk = chunk_blocks(h.cfg);
+    return (size_t)gacq_stap_workspace(&h.cfg);
+  });
 }
 
 extern "C" void gacq_stap_close(gacq_stap* h) { delete h; }
@@ -503,82 +407,43 @@ extern "C" void gacq_stap_close(gacq_stap* h) { delete h; }
 extern "C" int gacq_stap_run_dev(gacq_stap* h, const void* const* d_in, long long in_first, long long in_count, long long out_first, long long n_out,
                                  double gain, int out_complex64, void* d_out, void* d_stats, void* d_weights, void* d_cov) {
   if (!h) return GACQ_ERR_BAD_ARG;
-  gacq_ctx* ctx = h->ctx;
   const gacq_stap_cfg& c = h->cfg;
-  if (!d_in || !d_out) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_stap_run_dev: NULL argument");
-  for (int p = 0; p < c.antennas; p++)
-    if (!d_in[p]) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_stap_run_dev: the pointer of antenna %d is NULL", p);
-  // everything is checked before anything is launched
-  int rc = gacq_stap_check(&c, in_first, in_count, out_first, n_out, gain, out_complex64);
-  if (rc < 0) return st_forward(ctx, rc);
-  if (out_complex64 && (uintptr_t)d_out % 8u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_stap_run_dev: complex64 output must be 8-byte aligned");
-  if ((uintptr_t)d_stats % 8u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_stap_run_dev: d_stats must be 8-byte aligned");
-  if ((uintptr_t)d_weights % 4u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_stap_run_dev: d_weights must be 4-byte aligned");
-  if ((uintptr_t)d_cov % 8u) return set_error(ctx, GACQ_ERR_BAD_ARG, "gacq_stap_run_dev: d_cov must be 8-byte aligned");
-  if (n_out == 0) return GACQ_OK;
-  const int M = c.antennas, T = c.taps, N = M * T;
-  const long long Lb = c.block, W = c.window, out_end = out_first + n_out;
-  const long long own_first = (out_first + Lb - 1) / Lb;
-  int* dC = (int*)h->dev.p;
-  int* dWq = dC + (size_t)(h->chunk + W) * N * N * 2;
-  GACQ_DEVICE(ctx);
-  for (long long o = out_first; o < out_end;) {
-    const long long b0 = o / Lb, o_end = std::min(out_end, (b0 + h->chunk) * Lb), b_hi = (o_end - 1) / Lb;
-    // ---- the covariances the weights of blocks b0 .. b_hi need
-    StCovArgs cv;
-    const long long pb0 = std::max(b0 - W, 0ll);
-    for (int p = 0; p < kStMaxM; p++) cv.in[p] = (const uint8_t*)d_in[p < M ? p : 0] + (pb0 * Lb - in_first) * 2;
-    cv.C = dC;
-    cv.nblk = std::max(b_hi, W) - pb0;
-    cv.abs0 = pb0 * Lb;
-    cv.Lb = (int)Lb;
-    cv.M = M;
-    cv.T = T;
-    cv.N = N;
-    cv.nt = (2 * N + 15) / 16;
-    const long long nwg = (cv.nblk * cv.nt + kStBlock / 64 - 1) / (kStBlock / 64);
-    hipLaunchKernelGGL(stap_cov_kernel, dim3((unsigned)std::min<long long>(nwg, (long long)kStMaxGrid)), dim3(kStBlock), 0, ctx->stream, cv);
-    if ((rc = st_launched(ctx, "gacq_stap_run_dev")) < 0) return rc;
-    // ---- the weights of blocks b0 .. b_hi
-    StWgtArgs wg;
-    wg.C = dC;
-    wg.Wq = dWq;
-    wg.cov = (long long*)d_cov;
-    wg.wout = (int*)d_weights;
-    for (int i = 0; i < 2 * kStMaxM; i++) wg.c[i] = i < 2 * M ? c.c[i] : 0.0;
-    wg.b_first = b0;
-    wg.own_first = own_first;
-    wg.nblk = (int)(b_hi - b0 + 1);
-    wg.p_off = (int)(b0 - pb0);
-    wg.warm = (int)std::max(W - b0, 0ll);
-    wg.W = (int)W;
-    wg.M = M;
-    wg.T = T;
-    wg.N = N;
-    wg.shift = c.load_shift;
-    hipLaunchKernelGGL(stap_weights_kernel, dim3((unsigned)wg.nblk), dim3(kStBlock), 0, ctx->stream, wg);
-    if ((rc = st_launched(ctx, "gacq_stap_run_dev")) < 0) return rc;
-    // ---- the outputs o .. o_end - 1
-    StApplyArgs ap;
-    for (int p = 0; p < kStMaxM; p++) ap.in[p] = (const uint8_t*)d_in[p < M ? p : 0] + (o - in_first) * 2;
-    ap.out = (uint8_t*)d_out + (o - out_first) * (out_complex64 ? 8 : 2);
-    ap.Wq = dWq;
-    ap.stats = (unsigned long long*)d_stats;
-    ap.n = (int)(o_end - o);
-    ap.phase = (int)(o % kStTile);
-    ap.lo = (int)std::max(in_first - o, -(1ll << 30));
-    ap.hi = (int)std::min(in_first + in_count - o, 1ll << 30);
-    ap.boff = (int)(o - b0 * Lb);
-    ap.owned = (unsigned long long)((o_end + Lb - 1) / Lb - (o + Lb - 1) / Lb);
-    ap.s = (float)gain * (1.0f / (float)kStWq);
-    ap.Lb = (int)Lb;
-    ap.M = M;
-    const long long ntiles = (o_end - 1) / kStTile - o / kStTile + 1;
-    const unsigned grid = (unsigned)std::min<long long>(ntiles, (long long)kStMaxGrid);
-    if (out_complex64) launch_apply<true>(T, grid, ctx->stream, ap);
-    else launch_apply<false>(T, grid, ctx->stream, ap);
-    if ((rc = st_launched(ctx, "gacq_stap_run_dev")) < 0) return rc;
-    o = o_end;
-  }
-  return GACQ_OK;
+  const int T = c.taps, N = c.antennas * T;
+  hipStream_t stream = h->ctx->stream;
+  return ar_run_dev(
+      "gacq_stap_run_dev", *h, gacq_stap_check, ArRun{d_in, in_first, in_count, out_first, n_out, gain, out_complex64, d_out, d_stats, d_weights, d_cov},
+      h->chunk, (size_t)(h->chunk + c.window) * N * N * 2,
+      [&](const ArRun& r) {
+        StCovArgs cv;
+        cv.abs0 = r.pb0 * c.block;
+        ar_inputs(cv.in, r, c.antennas, cv.abs0);
+        cv.C = r.dC;
+        cv.nblk = r.ncov;
+        cv.Lb = c.block;
+        cv.M = c.antennas;
+        cv.T = T;
+        cv.N = N;
+        cv.nt = (2 * N + 15) / 16;
+        const long long nwg = (cv.nblk * cv.nt + kArBlock / 64 - 1) / (kArBlock / 64);
+        hipLaunchKernelGGL(stap_cov_kernel, dim3((unsigned)std::min<long long>(nwg, (long long)kArMaxGrid)), dim3(kArBlock), 0, stream, cv);
+      },
+      [&](const ArRun& r) {
+        StWgtArgs wg;
+        ar_fill_weights(wg, c, r);
+        wg.T = T;
+        wg.N = N;
+        hipLaunchKernelGGL(stap_weights_kernel, dim3((unsigned)wg.nblk), dim3(kArBlock), 0, stream, wg);
+      },
+      [&](const ArRun& r) {
+        StApplyArgs ap;
+        ar_fill_apply(ap, c, r);
+        ap.n = (int)(r.o_end - r.o);
+        ap.phase = (int)(r.o % kArTile);
+        ap.lo = (int)std::max(r.in_first - r.o, -(1ll << 30));
+        ap.hi = (int)std::min(r.in_first + r.in_count - r.o, 1ll << 30);
+        ap.boff = (int)(r.o - r.b0 * c.block);
+        if (r.out_complex64) launch_apply<true>(T, r.grid, stream, ap);
+        else launch_apply<false>(T, r.grid, stream, ap);
+      });
 }
+

@@ -1,7 +1,8 @@
-"""The host path that the recording converters share -- ingest, mitigate, ddc, requant, cancel, nulling: each is a filter from absolute
-input sample indices to absolute output sample indices ("the stream contract").  Here are the uploader, the chunk state
-machine, the open device handle, the pointer conventions of a launch, the block / window algebra, the file pump and the command-line
-shell; what a tool computes, its gacq_*_dev call, its parser and its report line stay in the tool's module."""
+"""The host path that the recording converters share -- ingest, mitigate, ddc, requant, cancel, nulling, stap: each is a filter from
+absolute input sample indices to absolute output sample indices ("the stream contract").  Here are the uploader, the chunk
+state machine, the open device handle, the pointer conventions of a launch, the block / window algebra, the file pump and the
+command-line shell; what a tool computes, its gacq_*_dev call, its parser and its report line stay in the tool's module (nulling and
+stap share theirs in arrayfilter.py)."""
 import contextlib
 import ctypes
 import math
@@ -153,7 +154,7 @@ def pump(pieces, start, fouts, per, window=0, size=len):
     """The file pump: start(held) is called once, with the pieces read so far, as soon as they measure `window` (or the input ends
     short of that), and returns feed; feed(piece) returns one tensor per file of fouts, whose bytes are written, for the held pieces and
     then for every further one.  `per`: tensor elements per sample.  The samples written per file, or None if no piece came.
-    The automatic gains differ and stay as they are: ddc and nulling give the window that holds their first 65536 outputs, so the gain
+    The automatic gains differ and stay as they are: ddc, nulling and stap give the window that holds their first 65536 outputs, so the gain
     does not depend on the piece size; ingest and mitigate give none and take the gain from the first piece, whatever it holds."""
     feed, held, n = None, [], [0] * len(fouts)
 

@@ -953,6 +953,7 @@ int gacq_cancel_dev(gacq_ctx* ctx, const gacq_cancel_sat* sats, int K, const gac
  * stream, asynchronous, without state between calls and without host synchronisation: calls on one handle are ordered by that stream.
  * The handle is closed before its context is destroyed.  gacq_null_tile: the output samples one workgroup owns (for tests; tiles begin
  * at absolute sample indices that are multiples of it, a lane's run of 8 samples at multiples of 8), or GACQ_ERR_BAD_ARG.
+ * The host path (these checks, the handle, the chunk loop) is csrc/gacq_arrayhost.h, which gacq_stap below shares.
  * ------------------------------------------------------------------------------------------- */
 typedef struct gacq_null_cfg {
   int antennas;                    /* M, 2..8 */

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import nulling_cases as NC
+import nulling_oracle as NO
 import stap_cases as C
 import stap_oracle as O
 from gnss_dsp_tools_amd import _native as nat
@@ -107,6 +108,34 @@ def test_one_tap_is_nulling(engine, M):
         for u, v in zip(a, b):
             assert u.shape == v.shape and u.dtype == v.dtype and bool((u == v).all()), (M, dtype)
     assert np.array_equal(b[1].cpu().numpy(), NC.reference(name)["wq"])
+
+
+@pytest.mark.gpu
+def test_one_tap_file_pump_is_nullings(engine, tmp_path):
+    """the command lines of both tools on the same two files, T = 1, in pieces of 100 bytes that cut samples' blocks and are held for the
+    automatic gain's window: the same output and trace bytes, the same gain, clipped and sample counts, lines that differ by ` taps 1`
+    alone, and the bytes of nulling_oracle.run -- at a fixed gain and at the automatic one"""
+    Lb, W, n = 64, 2, 5 * 64 + 37
+    xs = NC.recording(2, n, 90)                     # the seed was chosen on the CPU: the scaled weights keep 0.14 from a rounding tie
+    assert NO.run(xs, 0, 0, n, Lb, W)["margin"] >= NC.MARGIN
+    paths = [str(tmp_path / ("ant%d.iq" % p)) for p in range(2)]
+    for x, path in zip(xs, paths):
+        x.tofile(path)
+    for fixed in (["--gain", "2.5"], []):
+        got = {}
+        for tool, extra in ((nulling, []), (stap, ["--taps", "1"])):
+            out, trace = str(tmp_path / (tool.__name__ + ".iq")), str(tmp_path / (tool.__name__ + ".w"))
+            line = tool.run(extra + ["--block", str(Lb), "--window", str(W), "--weights-trace", trace, "--out", out] + fixed + paths, out=io.StringIO(),
+                            piece_bytes=100)
+            got[tool] = (line, open(out, "rb").read(), open(trace, "rb").read())
+        (nline, nout, ntrace), (sline, sout, strace) = got[nulling], got[stap]
+        assert sout == nout and strace == ntrace and len(ntrace) == 8 * 2 * -(-n // Lb)
+        assert sline.replace(" taps 1", "") == nline and sline != nline
+        nw, sw = nline.split(), sline.split()
+        gain, clipped, samples = float(nw[7]), int(nw[9]), int(nw[11])
+        assert (float(sw[9]), int(sw[11]), int(sw[13])) == (gain, clipped, samples) and samples == n and (gain == 2.5) == bool(fixed)
+        want = NO.run(xs, 0, 0, n, Lb, W, 10, None, gain)
+        assert nout == want["out"].tobytes() and clipped == want["clipped"], (fixed, gain)
 
 
 def _raw(sp, ds, in_first, out_first, n_out, cplx, out, stats, wq, cov, gain=2.5):
