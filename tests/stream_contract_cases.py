@@ -1,5 +1,5 @@
 """The case table of the device-side stream-contract tests (test_stream_contract_cpu.py, test_stream_contract_gpu.py): one adapter per
-recording converter -- ingest, mitigate, ddc, requant, cancel, nulling -- that gives a seeded recording, the module's one-call form, its
+recording converter -- ingest, mitigate, ddc, requant, cancel, nulling, stap -- that gives a seeded recording, the module's one-call form, its
 Chunks subclass, the oracle of tests/*_oracle.py with its comparison rule, and the oracle's needed / supported.  DESIGN.md 5.26 has the
 contract; every seed, cut and chunk list below is drawn from numpy.random.Generator(PCG64([SEED, the case's seed, a purpose number])).
 
@@ -27,8 +27,10 @@ import nulling_cases
 import nulling_oracle
 import requant_cases
 import requant_oracle
+import stap_cases
+import stap_oracle
 from gnss_dsp_tools_amd import _native as nat
-from gnss_dsp_tools_amd import cancel, ddc, ingest, mitigate, nulling, requant
+from gnss_dsp_tools_amd import cancel, ddc, ingest, mitigate, nulling, requant, stap
 
 SEED = 20261020
 BAD_ARG, SHORT_INPUT = -1, -6
@@ -615,10 +617,13 @@ class NullingCase(Case):
     def supported(self, in_first, in_count):
         return nulling_oracle.supported(self.Lb, self.W, in_first, in_count)
 
+    def _handle(self, engine):
+        return nulling.Nuller(engine, self.M, self.Lb, self.W, self.load_shift)
+
     @contextlib.contextmanager
     def open(self, engine, shift=0):
         torch = nat.require_torch()
-        with nulling.Nuller(engine, self.M, self.Lb, self.W, self.load_shift) as nl:
+        with self._handle(engine) as nl:
             seen = [0, 0]                                        # the handle's totals after the last run: nothing is read before a launch
 
             def run(ds, in_first, out_first, n_out, dtype):
@@ -658,9 +663,58 @@ class NullingCase(Case):
         return nat.lib.gacq_null_check(ctypes.addressof(c), in_first, in_count, out_first, n_out, self.gain, 0)
 
 
+# ---------------------------------------------------------------------------------------------- stap
+class StapCase(NullingCase):
+    """nulling's adapter with T taps on every antenna: t_c = (T - 1) / 2 samples more at either end of the input, N = M T weights a
+    block; the comparison rule is NullingCase.compare, that of test_stap_gpu.py.  The recordings are those of stap_cases "long"."""
+    tool = "stap"
+    tile, run_len = stap_cases.TILE, stap_cases.RUN
+
+    def __init__(self, name, long_name):
+        M, T, Lb, W, seed, kind = stap_cases.CASES[long_name]
+        assert kind == "long"
+        NullingCase.__init__(self, name, seed, M, Lb, W)
+        self.T, self.long_name = T, long_name
+
+    def recording(self):
+        return tuple(x.view(np.uint8) for x in stap_cases.data(self.long_name))
+
+    def first_needed(self, out_first):
+        return stap_oracle.needed(self.Lb, self.W, self.T, out_first, 1)[0]
+
+    def needed(self, out_first, n_out):
+        return stap_oracle.needed(self.Lb, self.W, self.T, out_first, n_out)
+
+    def supported(self, in_first, in_count):
+        return stap_oracle.supported(self.Lb, self.W, self.T, in_first, in_count)
+
+    def _handle(self, engine):
+        return stap.Stap(engine, self.M, self.T, self.Lb, self.W, self.load_shift)
+
+    def oracle(self, inputs, in_first, out_first, n_out, shift=0):
+        xs = [x.view(np.int8) for x in inputs]
+        return {dt: stap_oracle.run(xs, in_first, out_first, n_out, self.Lb, self.W, self.T, self.load_shift, None, self.gain, dt == "complex64")
+                for dt in self.dtypes}
+
+    def stream(self, engine, dtype):
+        torch = nat.require_torch()
+        s = stap.Stream(engine, self.M, self.gain, self.T, self.Lb, self.W, self.load_shift, None, dtype, weights=True)
+        return types.SimpleNamespace(feed=lambda chunks: [s.feed(chunks)], next_out=lambda: [s.next_out], stats=s.stats, close=s.close,
+                                     side=lambda: (host(torch.cat(s.traces)),))
+
+    def raw(self, engine, h, ds, in_first, in_count, out_first, n_out, out):
+        ptrs = (ctypes.c_void_p * self.M)(*[d.data_ptr() for d in ds])
+        return nat.lib.gacq_stap_run_dev(h.handle, ctypes.cast(ptrs, ctypes.c_void_p), in_first, in_count, out_first, n_out, self.gain, 0,
+                                         ctypes.c_void_p(out.data_ptr()), None, None, None)
+
+    def check(self, in_first, in_count, out_first, n_out, shift=0):
+        c = stap.make_cfg(self.M, self.T, self.Lb, self.W, self.load_shift)
+        return nat.lib.gacq_stap_check(ctypes.addressof(c), in_first, in_count, out_first, n_out, self.gain, 0)
+
+
 # the seeds of the mitigate and nulling cases were chosen here, on the CPU, so that the preconditions of their comparison rules hold
 # (test_stream_contract_cpu.py asserts them): the excision decisions keep 1e-4 from their thresholds, the scaled weights 1e-6 from a
-# rounding tie
+# rounding tie; the stap cases take the "long" recordings of stap_cases, whose seeds (80, 82) were chosen there by the same rule
 CASES = [
     IngestCase("ingest-2sm-real", "2sm", True, ingest_cases.REAL_GAIN["2sm"], 1),
     IngestCase("ingest-1ob-iq", "1ob", False, ingest_cases.IQ_GAIN["1ob"], 2),
@@ -673,8 +727,10 @@ CASES = [
     CancelCase("cancel-two-sats", 41),
     NullingCase("nulling-m3-b128-w3", 51, 3, 128, 3),
     NullingCase("nulling-m2-b192-w2", 52, 2, 192, 2),
+    StapCase("stap-m3-t3-b128-w3", "long-m3-t3-b128-w3"),
+    StapCase("stap-m1-t15-b192-w2", "long-m1-t15-b192-w2"),
 ]
-TOOLS = ("ingest", "mitigate", "ddc", "requant", "cancel", "nulling")
+TOOLS = ("ingest", "mitigate", "ddc", "requant", "cancel", "nulling", "stap")
 BY_NAME = {c.name: c for c in CASES}
 
 

@@ -1,6 +1,6 @@
 """CPU: what the device-side stream-contract tests (test_stream_contract_gpu.py) rest on, established without a device -- the case table
-covers the six tools and its drawn cuts and chunks have the properties the GPU tests count on; the new recordings satisfy the
-preconditions of the comparison rules they are held to (the nulling rounding-tie margin, the distance of the mitigate decisions from
+covers the seven tools and its drawn cuts and chunks have the properties the GPU tests count on; the new recordings satisfy the
+preconditions of the comparison rules they are held to (the nulling and stap rounding-tie margin, the distance of the mitigate decisions from
 their thresholds); needed() and supported() of every adapter agree with each other; the far-end call of every configuration is the
 last one its tool's gacq_*_check accepts; and tests/requant_oracle.evaluate, which gained in_first, gives what it gave."""
 import numpy as np
@@ -9,17 +9,22 @@ import pytest
 import nulling_cases
 import requant_cases
 import requant_oracle as RO
+import stap_oracle
 import stream_contract_cases as S
 from gnss_dsp_tools_amd import _native as nat
-from gnss_dsp_tools_amd import ingest, streaming
+from gnss_dsp_tools_amd import ingest, stap, streaming
 
 
-def test_the_table_covers_the_six_tools_and_their_configurations():
-    assert sorted(set(c.tool for c in S.CASES)) == sorted(S.TOOLS) and len(S.BY_NAME) == len(S.CASES)
+def test_the_table_covers_the_seven_tools_and_their_configurations():
+    assert sorted(set(c.tool for c in S.CASES)) == sorted(S.TOOLS) and len(S.BY_NAME) == len(S.CASES) == 13 and len(S.TOOLS) == 7
     names = set(S.BY_NAME)
     assert {"ingest-2sm-real", "ingest-1ob-iq", "ingest-s16-iq", "mitigate-n128-blank", "mitigate-blank-only", "ddc-d5-t3", "requant-u8", "requant-2sm",
-            "cancel-two-sats", "nulling-m3-b128-w3", "nulling-m2-b192-w2"} == names
+            "cancel-two-sats", "nulling-m3-b128-w3", "nulling-m2-b192-w2", "stap-m3-t3-b128-w3", "stap-m1-t15-b192-w2"} == names
     assert S.BY_NAME["ddc-d5-t3"].D % 2 == 1 and nulling_cases.TILE % 192 != 0
+    for name, (M, T, Lb, W, seed) in (("stap-m3-t3-b128-w3", (3, 3, 128, 3, 80)), ("stap-m1-t15-b192-w2", (1, 15, 192, 2, 82))):
+        c = S.BY_NAME[name]
+        assert (c.M, c.T, c.Lb, c.W, c.seed) == (M, T, Lb, W, seed) and c.shift_unit == Lb and c.block_edge == (W + 1) * Lb
+        assert c.n_in() == c.tile + 5 * Lb + 37 and c.total() == c.n_in() - stap_oracle.centre(T)
 
 
 @pytest.mark.parametrize("c", S.CASES, ids=S.case_id)
@@ -64,6 +69,8 @@ def test_the_near_call_lies_past_every_effect_of_sample_zero_and_its_shifts_stra
                 assert lo + c.ratio * s < 1 << k < lo + c.ratio * s + cnt - 1
     if c.tool in ("requant", "nulling"):
         assert lo % c.Lb == 0 and o >= (c.W + 1) * c.Lb                                # in_first on a block, outputs past the warm-up
+    if c.tool == "stap":
+        assert (lo + stap_oracle.centre(c.T)) % c.Lb == 0 and o >= (c.W + 1) * c.Lb    # in_first t_c before a block
 
 
 @pytest.mark.parametrize("c", [c for c in S.CASES if c.check is not None], ids=S.case_id)
@@ -105,11 +112,18 @@ def test_mitigate_decisions_of_the_new_recordings_keep_their_distance_from_the_t
     assert ref.blanked > 10 and ref.frames == 0 and len(np.unique(ref.i8)) > 30        # integer comparisons: no margin to keep
 
 
-@pytest.mark.parametrize("name", ["nulling-m3-b128-w3", "nulling-m2-b192-w2"])
+@pytest.mark.parametrize("name", ["nulling-m3-b128-w3", "nulling-m2-b192-w2", "stap-m3-t3-b128-w3", "stap-m1-t15-b192-w2"])
 def test_nulling_weights_of_the_new_recordings_keep_their_distance_from_a_rounding_tie(name):
-    """as nulling_cases.check_margins: no scaled weight component within 1e-6 of a half-integer, in any block"""
+    """as nulling_cases.check_margins and stap_cases.check_margins: no scaled weight component within 1e-6 of a half-integer, in any
+    block -- of the whole recording at the table's gain, and of the near call that the far calls shift, up to the far end that
+    gacq_*_check accepts (the oracle counts blocks by the absolute index, so this is the far call's margin too)"""
     c = S.BY_NAME[name]
     ref = c.oracle(c.recording(), 0, 0, c.total())
+    o, s = c.far_end(c.accepts)
+    lo, o, n, cnt = c.near_call(o)
+    assert c.check(lo + s, cnt, o + s, n, s) == 0 and c.check(lo + s + 1, cnt, o + s + 1, n, s + 1) == S.BAD_ARG
+    far = c.oracle(c.cut(*c.needed(o, n)), lo + s, o + s, n)
+    assert far["int8"]["margin"] >= nulling_cases.MARGIN and far["int8"]["owned"] > 50, (name, far["int8"]["margin"])
     for dt in c.dtypes:
         assert ref[dt]["margin"] >= nulling_cases.MARGIN, (name, ref[dt]["margin"])
         assert ref[dt]["owned"] == -(-c.total() // c.Lb)
@@ -140,6 +154,12 @@ def test_block_algebra_of_streaming_is_the_oracles():
             assert streaming.first_needed(c.Lb, c.W, out) == c.needed(out, 1)[0]
         for end in (0, c.W * c.Lb - 1, c.W * c.Lb, c.W * c.Lb + 1, 5 * c.Lb + 3, (1 << 32) + 3):
             assert streaming.out_end(c.Lb, c.W, end, unit) == c.supported(0, end) == c.supported(c.Lb, end - c.Lb)
+    for c in (S.BY_NAME["stap-m3-t3-b128-w3"], S.BY_NAME["stap-m1-t15-b192-w2"]):      # stap.py's own, t_c further at either end
+        for out in (0, 1, c.Lb - 1, c.Lb, c.W * c.Lb, c.W * c.Lb + 1, (c.W + 2) * c.Lb + 7, (1 << 32) + 5, (1 << 48) - 3):
+            assert stap.first_needed(c.Lb, c.W, out, c.T) == c.needed(out, 1)[0] == c.first_needed(out)
+        tc = stap_oracle.centre(c.T)
+        for end in (0, c.W * c.Lb - 1, c.W * c.Lb, c.W * c.Lb + tc - 1, c.W * c.Lb + tc, 5 * c.Lb + 3, (1 << 32) + 3):
+            assert stap.out_end(c.Lb, c.W, end, c.T) == c.supported(0, end) == c.supported(c.Lb, end - c.Lb)
 
 
 # ---- requant_oracle.evaluate with in_first: every existing call gives what it gave

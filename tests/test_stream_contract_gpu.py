@@ -1,4 +1,4 @@
-"""GPU: the six recording converters -- ingest, mitigate, ddc, requant, cancel, nulling -- held to the stream contract of DESIGN.md 5.26
+"""GPU: the seven recording converters -- ingest, mitigate, ddc, requant, cancel, nulling, stap -- held to the stream contract of DESIGN.md 5.26
 on the device, by one harness over the case table of tests/stream_contract_cases.py:
 
   far indices    every configuration in one call whose indices straddle 2^31, straddle 2^32 and end at the largest index its own
@@ -68,9 +68,9 @@ def _calls_of(engine, case, base):
 
 
 def test_the_table_covers_what_the_contract_names():
-    """the coverage of this file, asserted: six tools, three bases each, indices that cross 2^31 and 2^32, cuts at a tile edge and a
+    """the coverage of this file, asserted: seven tools, three bases each, indices that cross 2^31 and 2^32, cuts at a tile edge and a
     block edge, empty chunks and a first chunk that yields nothing"""
-    assert sorted(set(c.tool for c in S.CASES)) == sorted(S.TOOLS) and len(S.TOOLS) == 6
+    assert sorted(set(c.tool for c in S.CASES)) == sorted(S.TOOLS) and len(S.TOOLS) == 7
     assert S.BASES == ("2^31", "2^32", "far end") and all(sum(1 for c, b in BASE_CALLS if c.tool == t) >= 3 for t in S.TOOLS)
     for tool in S.TOOLS:
         cases = [c for c in S.CASES if c.tool == tool]
@@ -88,7 +88,8 @@ def test_the_table_covers_what_the_contract_names():
         sizes = c.chunk_sizes()
         assert 0 in sizes[1:] and any(a == 0 and b == 0 for a, b in zip(sizes, sizes[1:])) and max(c.ends(0, c.samples(sizes[0]))) == 0, c.name
     # the tools that count blocks cut at a block edge; ingest, ddc and the blank-only path have none, cancel's is its segment edge
-    assert all(c.block_edge is not None for c in S.CASES if c.tool in ("requant", "nulling", "cancel")) and S.BY_NAME["mitigate-n128-blank"].block_edge
+    assert all(c.block_edge is not None for c in S.CASES if c.tool in ("requant", "nulling", "stap", "cancel")) and S.BY_NAME["mitigate-n128-blank"].block_edge
+    assert all(c.block_edge == (c.W + 1) * c.Lb and c.shift_unit == c.Lb for c in S.CASES if c.tool in ("nulling", "stap"))
 
 
 @pytest.mark.gpu
@@ -264,7 +265,7 @@ def _behind_a_delayed_producer(eng, case, h, base, side, before=None):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", [S.BY_NAME[n] for n in ("ingest-2sm-real", "mitigate-n128-blank", "ddc-d5-t3", "requant-2sm", "cancel-two-sats",
-                                                         "nulling-m3-b128-w3")], ids=S.case_id)
+                                                         "nulling-m3-b128-w3", "stap-m3-t3-b128-w3")], ids=S.case_id)
 def test_the_call_runs_on_torchs_current_stream(case):
     torch = nat.require_torch()
     side = _side_streams()[0]
@@ -289,7 +290,8 @@ def _spectrum_first(eng, s1):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("first,second", [("spectrum", "ingest-s16-iq"), ("cancel-two-sats", "nulling-m2-b192-w2"), ("requant-u8", "mitigate-blank-only")])
+@pytest.mark.parametrize("first,second", [("spectrum", "ingest-s16-iq"), ("cancel-two-sats", "nulling-m2-b192-w2"), ("requant-u8", "mitigate-blank-only"),
+                                          ("nulling-m3-b128-w3", "stap-m1-t15-b192-w2")])
 def test_the_stream_the_last_tool_left_behind_does_not_stick(first, second):
     """tool A under side stream s1, then tool B under s2 behind its own delayed producer, on one engine: B sees its real input"""
     torch = nat.require_torch()
