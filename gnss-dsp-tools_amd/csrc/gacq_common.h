@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <rocfft/rocfft.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <map>
@@ -229,6 +230,18 @@ int verify_search(gacq_sig* sig, const SearchPlan& plan, XSrc d_x, size_t nsamp,
                   float* d_qrow);
 void stage_begin(gacq_ctx* ctx, int stage);
 void stage_end(gacq_ctx* ctx);
+// one stage of a search under its stage timer (gacq_get_stage_time); stage < 0: untimed (the complex128 rocFFT form records none)
+template <class Run> int timed(gacq_ctx* ctx, int stage, Run run) {
+  if (stage < 0) return run();
+  stage_begin(ctx, stage);
+  const int rc = run();
+  stage_end(ctx);
+  return rc;
+}
+// epochs per pass of a search, so that the forward spectra of one pass (x_epoch_bytes an epoch) respect the workspace budget
+inline int epochs_per_pass(gacq_ctx* ctx, int nepoch, size_t x_epoch_bytes) {
+  return (int)std::max<size_t>(1, std::min<size_t>((size_t)nepoch, ws_budget(ctx) / std::max<size_t>(1, x_epoch_bytes)));
+}
 
 // LDS-resident FFT engine: the lengths it serves (4096 and 16384), and the launches of the N = 4096 kernels (gacq_ldsfft.hip).
 bool lds_supported(int N);

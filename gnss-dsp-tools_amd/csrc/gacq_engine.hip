@@ -148,7 +148,8 @@ size_t ws_budget(gacq_ctx* ctx) {
     if (ctx->ws_soft == 0 || nctx > ctx->ws_soft_nctx) {
       // A context holds up to two buffers of this size (forward spectra X, correlation workspace Y), each with 1/8 of headroom.  What is
       // free now plus what this context already holds, a fifth of it left to everything else on the device, split evenly over the
-      // contexts: 102 GB for a lone context on an empty 288 GB part (the 32 GiB limit binds), 13 GB each for eight ranks sharing one.
+      // contexts of this process: 102 GB for a lone context on an empty 288 GB part (the 32 GiB limit binds), 13 GB each for eight.
+      // Other processes on the device (one per rank) are not counted: each sees what is free when it first looks.
       size_t free_b = 0, total_b = 0;
       if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
         ctx->ws_soft = std::max<size_t>((size_t)64 << 20, (size_t)((double)(free_b + ctx->X.cap + ctx->Y.cap) * 0.8 / 2.25 / nctx));
@@ -959,9 +960,6 @@ int upload_grid(gacq_sig* sig, int nepoch, const int* items, int nitems, const d
   return GACQ_OK;
 }
 
-// one stage of a search under its stage timer (gacq_get_stage_time)
-template <class Run> int timed(gacq_ctx* ctx, int stage, Run run) { stage_begin(ctx, stage); const int rc = run(); stage_end(ctx); return rc; }
-
 // xs: the samples as the caller gave them (complex64 or complex128); d_x: their complex64 form for the fp32 engines (== xs.p for
 // complex64 input, a rounded copy for complex128 input, unused by engine 5)
 int launch_search(gacq_sig* sig, XSrc xs, const float2* d_x, size_t nsamp, int nepoch, const int* items, int nitems,
@@ -994,7 +992,7 @@ int launch_search(gacq_sig* sig, XSrc xs, const float2* d_x, size_t nsamp, int n
   // epochs per pass so that the forward-spectra buffer respects the workspace limit; the fused forms buffer nothing but the 16-byte
   // row records
   const size_t x_epoch_bytes = sizeof(float2) * (size_t)F * D * B * N;
-  const int Ec = plan.fused() ? nepoch : (int)std::max<size_t>(1, std::min<size_t>((size_t)nepoch, ws_budget(ctx) / std::max<size_t>(1, x_epoch_bytes)));
+  const int Ec = plan.fused() ? nepoch : epochs_per_pass(ctx, nepoch, x_epoch_bytes);
   if (!plan.fused() && (rc = ensure(ctx, ctx->X, x_epoch_bytes * Ec)) != GACQ_OK) return rc;
   if ((rc = ensure(ctx, ctx->rows, sizeof(RowRec) * (size_t)Ec * P * D)) != GACQ_OK) return rc;
 

@@ -1,10 +1,17 @@
 // Engine 5: complex128 verification pipeline (hard part 1: "keep a complex128 build").
 //
 // The product engines compute in complex64; the reference computes in complex128 (numpy / scipy.fftpack).  This engine is the
-// north-star pipeline K1 -> FFT -> K2 -> IFFT -> K3 -> K4 with every value in fp64 on the device (rocFFT double precision, fp64
-// NCO table, fp64 magnitudes and metric), so it agrees with the reference to ~1e-12 instead of ~1e-7.  It exists to bisect:
-// when an fp32 engine and the oracle disagree on a near-tied peak, engine 5 says which side the rounding fell on.  Slow by
-// design (twice the bytes, a quarter of the flops/s); selected only by gacq_set_engine(ctx, 5), never by auto.
+// north-star pipeline K1 -> FFT -> K2 -> IFFT -> K3 -> K4 with every value in fp64 on the device (fp64 NCO table, transforms,
+// magnitudes and metric), so it agrees with the reference to ~1e-12 instead of ~1e-7.  It exists to bisect: when an fp32 engine
+// and the oracle disagree on a near-tied peak, engine 5 says which side the rounding fell on.  Selected only by
+// gacq_set_engine(ctx, 5), never by auto.  plan_search (gacq_engine.hip) picks one of five forms, verify_search runs them all on
+// one host path:
+//   C128Fused4k  N = 4096, B = 1, one carrier: the whole search row in one kernel (fused4k_c128_kernel)
+//   C128Lds4k    N = 4096 otherwise: a forward and a correlate kernel on the LDS-resident transform (c128_4k_*_kernel)
+//   C128Split    N = 4 x 4096 / 16 x 4096: outer DFT-R around the resident transform, one Z' round trip (c128_split_*_kernel)
+//   C128R31      N = 31 x M (61380, 30690): fp64 DFT-31 stages around rocFFT's native length-M transforms (c128_r31_*_kernel)
+//   C128Rocfft   every other length, row dumps of N = 4096 and GACQ_OPT_FUSED_C128 = 0: the five-stage pipeline on rocFFT's
+//                double-precision transforms, the cross-check of the other four
 #include "gacq_common.h"
 #define GACQ_F64_UNPAIR 1      // fused4k_c128_kernel: no AGPR spills (244 VGPRs), see gacq_fft64.h
 #include "gacq_fft64.h"
@@ -719,269 +726,153 @@ int verify_spectra(gacq_sig* s) {
   return GACQ_OK;
 }
 
-// the split form of engine 5 (N = 4 x 4096 or 16 x 4096): see c128_split_*_kernel
-template <int R>
-static int split64_search(gacq_sig* sig, XSrc d_x, size_t nsamp, int nepoch, int P, int F, int D, int B, gacq_peak* d_out, float* d_qrow,
-                          const double2* tab) {
+// the code spectra in the order the R x M forms read them (c128_split_spectra_kernel), published only once the reorder has run
+static int split_spectra64(gacq_sig* sig, int R, int M, const char* what) {
+  if (sig->spectra64_split) return GACQ_OK;
   gacq_ctx* ctx = sig->ctx;
-  hipStream_t st = ctx->stream;
-  const int n = sig->desc.n, N = sig->N;
-  int rc;
-  const double2* WN;
-  if ((rc = twiddles64(ctx, N, &WN)) != GACQ_OK) return rc;
-  if (!sig->spectra64_split) {
-    double2* buf = nullptr;
-    GACQ_HIP(ctx, hipMalloc((void**)&buf, sizeof(double2) * (size_t)sig->nprn * N));
-    hipLaunchKernelGGL(c128_split_spectra_kernel, dim3((unsigned)(sig->nprn * R)), dim3(kBlock), 0, st, (const double2*)sig->spectra64, buf, R, f64::kN);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-      (void)hipFree(buf);
-      return set_error(ctx, GACQ_ERR_HIP, "complex128 split engine: code-spectrum reorder failed");
-    }
-    sig->spectra64_split = buf;
+  double2* buf = nullptr;
+  GACQ_HIP(ctx, hipMalloc((void**)&buf, sizeof(double2) * (size_t)sig->nprn * sig->N));
+  hipLaunchKernelGGL(c128_split_spectra_kernel, dim3((unsigned)(sig->nprn * R)), dim3(kBlock), 0, ctx->stream, (const double2*)sig->spectra64, buf, R, M);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+    (void)hipFree(buf);
+    return set_error(ctx, GACQ_ERR_HIP, "%s: code-spectrum reorder failed", what);
   }
-  GACQ_HIP(ctx, hipFuncSetAttribute((const void*)c128_split_forward_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, f64::kLdsBytes));
-  GACQ_HIP(ctx, hipFuncSetAttribute((const void*)c128_split_corr_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, f64::kLdsBytes));
-  const size_t x_epoch_bytes = sizeof(double2) * (size_t)F * D * B * N;
-  const int Ec = (int)std::max<size_t>(1, std::min<size_t>((size_t)nepoch, ws_budget(ctx) / std::max<size_t>(1, x_epoch_bytes)));
-  if ((rc = ensure(ctx, ctx->X, x_epoch_bytes * Ec)) != GACQ_OK) return rc;
-  if ((rc = ensure(ctx, ctx->rows, sizeof(RowRec64) * (size_t)Ec * P * D)) != GACQ_OK) return rc;
-  // items per writer workgroup: the forward-spectrum row stays in registers over them (one carrier); with a carrier per item (GLONASS)
-  // every item has its own row and nothing is shared
-  const int pch = (F == 1) ? std::min(P, 8) : 1;
-  const int nchunk = (P + pch - 1) / pch;
-  for (int e0 = 0; e0 < nepoch; e0 += Ec) {
-    const int ne = std::min(Ec, nepoch - e0);
-    double2* Xs = (double2*)ctx->X.p;
-    RowRec64* rows = (RowRec64*)ctx->rows.p;
-    const long rows_x = (long)ne * F * D * B;
-    const unsigned cols = (unsigned)(N / kBlock);
-    if (rows_x * cols >= (1L << 31)) return set_error(ctx, GACQ_ERR_UNSUPPORTED, "complex128 split engine: too many forward rows in one pass (lower the workspace limit)");
-    // carrier wipe-off into the correlation workspace (free until the first Z' pass), then the split forward transform out of it
-    if ((rc = ensure(ctx, ctx->Y, x_epoch_bytes * ne)) != GACQ_OK) return rc;
-    stage_begin(ctx, 0);
-    hipLaunchKernelGGL(mix64_kernel, dim3((unsigned)(rows_x * cols)), dim3(kBlock), 0, st, d_x.offset((size_t)e0 * nsamp), nsamp, (double2*)ctx->Y.p,
-                       (const double*)ctx->freq.p, tab, n, N, F * D, B, cols);
-    GACQ_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(c128_split_forward_kernel<R>, dim3((unsigned)(((rows_x + 7) / 8) * 8 * R)), dim3(kBlock), f64::kLdsBytes, st, (const double2*)ctx->Y.p, Xs, WN,
-                       (unsigned)rows_x);
-    stage_end(ctx);
-    GACQ_HIP(ctx, hipGetLastError());
-    // Z' passes of whole (epoch, Doppler bin) units, P items each: at most 4 GiB a pass, as in the fp32 split engines
-    const long units = (long)ne * D;
-    const size_t unit_bytes = sizeof(double2) * (size_t)P * B * N;
-    const size_t pass_cap = std::min(ws_budget(ctx), std::max<size_t>((size_t)4 << 30, unit_bytes));
-    long uc = (long)std::max<size_t>(1, std::min<size_t>((size_t)units, pass_cap / unit_bytes));
-    uc = std::min<long>(uc, std::max<long>(1, ((1L << 31) - 1) / ((long)B * R * nchunk)));
-    if (d_qrow) uc = 1;
-    if ((rc = ensure(ctx, ctx->Y, unit_bytes * uc)) != GACQ_OK) return rc;
-    double2* Z = (double2*)ctx->Y.p;
-    for (long u0 = 0; u0 < units; u0 += uc) {
-      const long nu = std::min(uc, units - u0);
-      stage_begin(ctx, 6);
-      hipLaunchKernelGGL(c128_split_corr_kernel<R>, dim3((unsigned)(nu * B * nchunk * R)), dim3(kBlock), f64::kLdsBytes, st, (const double2*)Xs,
-                         (const double2*)sig->spectra64_split, Z, (const int*)ctx->items.p, (const int*)ctx->fset.p, WN, u0, P, F, D, B, pch, nchunk);
-      stage_end(ctx);
-      GACQ_HIP(ctx, hipGetLastError());
-      stage_begin(ctx, 4);
-      hipLaunchKernelGGL(c128_split_reader_kernel<R>, dim3((unsigned)(nu * P)), dim3(kBlock), 0, st, (const double2*)Z, rows, u0, P, D, B, d_qrow);
-      stage_end(ctx);
-      GACQ_HIP(ctx, hipGetLastError());
-    }
-    const long nep = (long)ne * P;
-    stage_begin(ctx, 5);
-    hipLaunchKernelGGL(best_doppler64_kernel, dim3((unsigned)((nep + 63) / 64)), dim3(64), 0, st, (const RowRec64*)rows, d_out + (size_t)e0 * P, nep, D, N,
-                       sig->desc.metric_mode);
-    stage_end(ctx);
-    GACQ_HIP(ctx, hipGetLastError());
-  }
+  sig->spectra64_split = buf;
   return GACQ_OK;
 }
 
-// the N = 31 x M form of engine 5: see c128_r31_*_kernel
-static int r31_64_search(gacq_sig* sig, XSrc d_x, size_t nsamp, int nepoch, int P, int F, int D, int B, gacq_peak* d_out, float* d_qrow,
-                         const double2* tab) {
-  gacq_ctx* ctx = sig->ctx;
-  hipStream_t st = ctx->stream;
-  const int n = sig->desc.n, N = sig->N, M = N / 31;
-  int rc;
-  const double2* WN;
-  if ((rc = twiddles64(ctx, N, &WN)) != GACQ_OK) return rc;
-  if (!sig->spectra64_split) {
-    double2* buf = nullptr;
-    GACQ_HIP(ctx, hipMalloc((void**)&buf, sizeof(double2) * (size_t)sig->nprn * N));
-    hipLaunchKernelGGL(c128_split_spectra_kernel, dim3((unsigned)(sig->nprn * 31)), dim3(kBlock), 0, st, (const double2*)sig->spectra64, buf, 31, M);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-      (void)hipFree(buf);
-      return set_error(ctx, GACQ_ERR_HIP, "complex128 radix-31 engine: code-spectrum reorder failed");
-    }
-    sig->spectra64_split = buf;
-  }
-  const size_t x_epoch_bytes = sizeof(double2) * (size_t)F * D * B * N;
-  const int Ec = (int)std::max<size_t>(1, std::min<size_t>((size_t)nepoch, ws_budget(ctx) / std::max<size_t>(1, x_epoch_bytes)));
-  if ((rc = ensure(ctx, ctx->X, x_epoch_bytes * Ec)) != GACQ_OK) return rc;
-  if ((rc = ensure(ctx, ctx->rows, sizeof(RowRec64) * (size_t)Ec * P * D)) != GACQ_OK) return rc;
-  const unsigned cols = (unsigned)((N + kBlock - 1) / kBlock);
-  const int chunks = (M + kBlock - 1) / kBlock;
-  for (int e0 = 0; e0 < nepoch; e0 += Ec) {
-    const int ne = std::min(Ec, nepoch - e0);
-    double2* X = (double2*)ctx->X.p;
-    RowRec64* rows = (RowRec64*)ctx->rows.p;
-    const long rows_x = (long)ne * F * D * B;
-    if (rows_x * cols >= (1L << 31)) return set_error(ctx, GACQ_ERR_UNSUPPORTED, "complex128 radix-31 engine: too many forward rows in one pass (lower the workspace limit)");
-    if ((rc = ensure(ctx, ctx->Y, x_epoch_bytes * ne)) != GACQ_OK) return rc;
-    stage_begin(ctx, 0);
-    hipLaunchKernelGGL(mix64_kernel, dim3((unsigned)(rows_x * cols)), dim3(kBlock), 0, st, d_x.offset((size_t)e0 * nsamp), nsamp, (double2*)ctx->Y.p,
-                       (const double*)ctx->freq.p, tab, n, N, F * D, B, cols);
-    GACQ_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(c128_r31_forward_kernel, dim3((unsigned)(rows_x * chunks)), dim3(kBlock), 0, st, (const double2*)ctx->Y.p, X, WN, M, chunks);
-    stage_end(ctx);
-    GACQ_HIP(ctx, hipGetLastError());
-    stage_begin(ctx, 1);
-    rc = fft_exec(ctx, M, rows_x * 31, false, X, true);
-    stage_end(ctx);
-    if (rc != GACQ_OK) return rc;
-    const long groups = (long)ne * P * D;
-    const size_t group_bytes = sizeof(double2) * (size_t)B * N;
-    const size_t pass_cap = std::min(ws_budget(ctx), std::max<size_t>((size_t)4 << 30, 8 * group_bytes * (size_t)D));
-    long gc = (long)std::max<size_t>(1, std::min<size_t>((size_t)groups, pass_cap / group_bytes));
-    gc = std::min<long>(gc, std::max<long>(1, ((1L << 31) - 1) / ((long)B * cols)));
-    if (d_qrow) gc = 1;
-    if ((rc = ensure(ctx, ctx->Y, group_bytes * gc)) != GACQ_OK) return rc;
-    double2* Y = (double2*)ctx->Y.p;
-    for (long g0 = 0; g0 < groups; g0 += gc) {
-      const long ng = std::min(gc, groups - g0);
-      stage_begin(ctx, 2);
-      hipLaunchKernelGGL(conj_mul64_kernel, dim3((unsigned)(ng * B * cols)), dim3(kBlock), 0, st, (const double2*)X, (const double2*)sig->spectra64_split, Y,
-                         (const int*)ctx->items.p, (const int*)ctx->fset.p, g0, P, F, D, B, N, cols);
-      stage_end(ctx);
-      GACQ_HIP(ctx, hipGetLastError());
-      stage_begin(ctx, 3);
-      rc = fft_exec(ctx, M, ng * B * 31, true, Y, true);
-      stage_end(ctx);
-      if (rc != GACQ_OK) return rc;
-      stage_begin(ctx, 4);
-      hipLaunchKernelGGL(c128_r31_reader_kernel, dim3((unsigned)ng), dim3(kBlock), 0, st, (const double2*)Y, rows, WN, g0, M, B, d_qrow);
-      stage_end(ctx);
-      GACQ_HIP(ctx, hipGetLastError());
-    }
-    const long nep = (long)ne * P;
-    stage_begin(ctx, 5);
-    hipLaunchKernelGGL(best_doppler64_kernel, dim3((unsigned)((nep + 63) / 64)), dim3(64), 0, st, (const RowRec64*)rows, d_out + (size_t)e0 * P, nep, D, N,
-                       sig->desc.metric_mode);
-    stage_end(ctx);
-    GACQ_HIP(ctx, hipGetLastError());
-  }
-  return GACQ_OK;
-}
+// the split form's kernels for one outer radix (N = 4 x 4096 or 16 x 4096)
+struct SplitKernels {
+  decltype(&c128_split_forward_kernel<4>) forward;
+  decltype(&c128_split_corr_kernel<4>) corr;
+  decltype(&c128_split_reader_kernel<4>) reader;
+};
+template <int R> static SplitKernels split_kernels() { return {c128_split_forward_kernel<R>, c128_split_corr_kernel<R>, c128_split_reader_kernel<R>}; }
 
+// One host path for the five forms, in the shape of launch_search: prepare, size the epoch pass, then per epoch pass the form's forward
+// stage, the Z' passes of the forms with a Z' round trip (writer, inverse, reader) and one Doppler scan.
 int verify_search(gacq_sig* sig, const SearchPlan& plan, XSrc d_x, size_t nsamp, int nepoch, int P, int F, int D, int B, gacq_peak* d_out,
                   float* d_qrow) {
   gacq_ctx* ctx = sig->ctx;
   hipStream_t st = ctx->stream;
   const int n = sig->desc.n, N = sig->N;
+  const Form form = plan.form;
+  const bool fused = form == Form::C128Fused4k, lds4k = form == Form::C128Lds4k, split = form == Form::C128Split, r31 = form == Form::C128R31;
+  const bool rocfft = form == Form::C128Rocfft;
+  const char* what = split ? "complex128 split engine" : r31 ? "complex128 radix-31 engine" : "verification engine";
+  const auto stage = [rocfft](int s) { return rocfft ? -1 : s; };      // the rocFFT form records no stage times
+  // one kernel on the search's stream under stage timer s (s < 0: inside a stage of its caller)
+  const auto launch = [&](int s, auto kernel, long grid, int block, size_t lds, auto... args) {
+    return timed(ctx, stage(s), [&] {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), lds, st, args...);
+      GACQ_HIP(ctx, hipGetLastError());
+      return (int)GACQ_OK;
+    });
+  };
   int rc;
   if ((rc = verify_spectra(sig)) != GACQ_OK) return rc;
   const double2* tab;
   if ((rc = nco_table64(ctx, &tab)) != GACQ_OK) return rc;
-  const double2* tw = nullptr;      // N = 4096: the resident transform's twiddles
-  if ((plan.form == Form::C128Fused4k || plan.form == Form::C128Lds4k) && (rc = twiddle64_4096(ctx, &tw)) != GACQ_OK) return rc;
-  switch (plan.form) {
-  case Form::C128Fused4k: {
-    // one kernel per search instead of the five-stage pipeline: the row never leaves the workgroup
-    if ((rc = ensure(ctx, ctx->rows, sizeof(RowRec64) * (size_t)nepoch * P * D)) != GACQ_OK) return rc;
-    RowRec64* rows = (RowRec64*)ctx->rows.p;
-    // one forward transform per workgroup: amortised over up to 32 items while >= ~1024 workgroups remain (2 resident per CU)
-    int pch = 4;
+  // N = R x M: the split form's outer radix 4 / 16 over the resident 4096-point transform; 31 x M around rocFFT's length-M transforms (M in its
+  // native radices: no Bluestein); 1 x N, rocFFT's own length-N transform
+  const int R = split ? N / f64::kN : r31 ? 31 : 1, M = N / R;
+  const double2* tw = nullptr;      // W_4096 of the resident transform (N = 4096) / W_N of the outer stage (split, radix-31)
+  if ((fused || lds4k) && (rc = twiddle64_4096(ctx, &tw)) != GACQ_OK) return rc;
+  if ((split || r31) && ((rc = twiddles64(ctx, N, &tw)) != GACQ_OK || (rc = split_spectra64(sig, R, M, what)) != GACQ_OK)) return rc;
+  const double2* C = (const double2*)(split || r31 ? sig->spectra64_split : sig->spectra64);
+  const SplitKernels sk = R == 4 ? split_kernels<4>() : split_kernels<16>();
+  const void* lds_kernels[2] = {nullptr, nullptr};      // the form's kernels on the resident transform: 64 KiB of dynamic LDS
+  if (fused) lds_kernels[0] = (const void*)fused4k_c128_kernel;
+  if (lds4k) { lds_kernels[0] = (const void*)c128_4k_forward_kernel; lds_kernels[1] = (const void*)c128_4k_correlate_kernel; }
+  if (split) { lds_kernels[0] = (const void*)sk.forward; lds_kernels[1] = (const void*)sk.corr; }
+  for (const void* k : lds_kernels)
+    if (k) GACQ_HIP(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, f64::kLdsBytes));
+
+  // epochs per pass so that the forward-spectra buffer respects the workspace limit; the fused form buffers nothing but the row records
+  const size_t x_epoch_bytes = sizeof(double2) * (size_t)F * D * B * N;
+  const int Ec = fused ? nepoch : epochs_per_pass(ctx, nepoch, x_epoch_bytes);
+  if (!fused && (rc = ensure(ctx, ctx->X, x_epoch_bytes * Ec)) != GACQ_OK) return rc;
+  if ((rc = ensure(ctx, ctx->rows, sizeof(RowRec64) * (size_t)Ec * P * D)) != GACQ_OK) return rc;
+
+  // items per workgroup.  Fused: one forward transform per workgroup, amortised over up to 32 items while >= ~1024 workgroups remain (2
+  // resident per CU).  Split writer: the forward-spectrum row stays in registers over its items (one carrier); with a carrier per item
+  // (GLONASS) every item has its own row and nothing is shared.
+  int pch = 1;
+  if (fused) {
+    pch = 4;
     while (pch < 32 && (long)nepoch * D * ((P + 2 * pch - 1) / (2 * pch)) >= 1024) pch *= 2;
     pch = std::min(pch, P);
-    const int nchunk = (P + pch - 1) / pch;
-    const long e8 = (nepoch + 7) / 8;
-    GACQ_HIP(ctx, hipFuncSetAttribute((const void*)fused4k_c128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, gacq::f64::kLdsBytes));
-    stage_begin(ctx, 6);
-    hipLaunchKernelGGL(fused4k_c128_kernel, dim3((unsigned)(8 * e8 * D * nchunk)), dim3(kBlock), gacq::f64::kLdsBytes, st, d_x, nsamp,
-                       (const double2*)sig->spectra64, (const int*)ctx->items.p, (const double*)ctx->freq.p, tab, tw, rows, nepoch, P, D, pch, nchunk);
-    stage_end(ctx);
-    GACQ_HIP(ctx, hipGetLastError());
-    const long nep = (long)nepoch * P;
-    stage_begin(ctx, 5);
-    hipLaunchKernelGGL(best_doppler64_kernel, dim3((unsigned)((nep + 63) / 64)), dim3(64), 0, st, (const RowRec64*)rows, d_out, nep, D, N, sig->desc.metric_mode);
-    stage_end(ctx);
-    GACQ_HIP(ctx, hipGetLastError());
-    return GACQ_OK;
+  } else if (split && F == 1) {
+    pch = std::min(P, 8);
   }
-  case Form::C128Lds4k: {
-    // several blocks or carriers: forward spectra once, then one workgroup per (epoch, Doppler bin, item) over its B rows
-    const size_t x_epoch_bytes = sizeof(double2) * (size_t)F * D * B * N;
-    const int Ec = (int)std::max<size_t>(1, std::min<size_t>((size_t)nepoch, ws_budget(ctx) / std::max<size_t>(1, x_epoch_bytes)));
-    if ((rc = ensure(ctx, ctx->X, x_epoch_bytes * Ec)) != GACQ_OK) return rc;
-    if ((rc = ensure(ctx, ctx->rows, sizeof(RowRec64) * (size_t)Ec * P * D)) != GACQ_OK) return rc;
-    GACQ_HIP(ctx, hipFuncSetAttribute((const void*)c128_4k_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, gacq::f64::kLdsBytes));
-    GACQ_HIP(ctx, hipFuncSetAttribute((const void*)c128_4k_correlate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, gacq::f64::kLdsBytes));
-    for (int e0 = 0; e0 < nepoch; e0 += Ec) {
-      const int ne = std::min(Ec, nepoch - e0);
-      RowRec64* rows = (RowRec64*)ctx->rows.p;
-      const long rows_x = (long)ne * F * D * B;
-      stage_begin(ctx, 0);
-      hipLaunchKernelGGL(c128_4k_forward_kernel, dim3((unsigned)rows_x), dim3(kBlock), gacq::f64::kLdsBytes, st, d_x.offset((size_t)e0 * nsamp), nsamp, (double2*)ctx->X.p,
-                         (const double*)ctx->freq.p, tab, tw, n, F * D, B);
-      stage_end(ctx);
-      GACQ_HIP(ctx, hipGetLastError());
-      const long units8 = ((long)ne * D + 7) / 8;
-      stage_begin(ctx, 6);
-      hipLaunchKernelGGL(c128_4k_correlate_kernel, dim3((unsigned)(8 * units8 * P)), dim3(kBlock), gacq::f64::kLdsBytes, st, (const double2*)ctx->X.p,
-                         (const double2*)sig->spectra64, (const int*)ctx->items.p, (const int*)ctx->fset.p, tw, rows, ne, P, F, D, B);
-      stage_end(ctx);
-      GACQ_HIP(ctx, hipGetLastError());
-      const long nep = (long)ne * P;
-      stage_begin(ctx, 5);
-      hipLaunchKernelGGL(best_doppler64_kernel, dim3((unsigned)((nep + 63) / 64)), dim3(64), 0, st, (const RowRec64*)rows, d_out + (size_t)e0 * P, nep, D, N, sig->desc.metric_mode);
-      stage_end(ctx);
-      GACQ_HIP(ctx, hipGetLastError());
-    }
-    return GACQ_OK;
-  }
-  // N = 4 x 4096 / 16 x 4096: the hand-written split form (one Z' round trip, no rocFFT plan)
-  case Form::C128Split:
-    return N == 4 * f64::kN ? split64_search<4>(sig, d_x, nsamp, nepoch, P, F, D, B, d_out, d_qrow, tab)
-                            : split64_search<16>(sig, d_x, nsamp, nepoch, P, F, D, B, d_out, d_qrow, tab);
-  // N = 31 x M with M in rocFFT's native radices (61380, 30690): the prime stays out of rocFFT (no Bluestein)
-  case Form::C128R31: return r31_64_search(sig, d_x, nsamp, nepoch, P, F, D, B, d_out, d_qrow, tab);
-  default: break;      // Form::C128Rocfft
-  }
-  const size_t x_epoch_bytes = sizeof(double2) * (size_t)F * D * B * N;
-  const int Ec = (int)std::max<size_t>(1, std::min<size_t>((size_t)nepoch, ws_budget(ctx) / std::max<size_t>(1, x_epoch_bytes)));
-  if ((rc = ensure(ctx, ctx->X, x_epoch_bytes * Ec)) != GACQ_OK) return rc;
-  if ((rc = ensure(ctx, ctx->rows, sizeof(RowRec64) * (size_t)Ec * P * D)) != GACQ_OK) return rc;
+  const int nchunk = (P + pch - 1) / pch;
   const unsigned cols = (unsigned)((N + kBlock - 1) / kBlock);
+  const int chunksM = (M + kBlock - 1) / kBlock;
+  const int* d_items = (const int*)ctx->items.p;
+  const int* d_fset = (const int*)ctx->fset.p;
+  const double* d_freq = (const double*)ctx->freq.p;
   for (int e0 = 0; e0 < nepoch; e0 += Ec) {
     const int ne = std::min(Ec, nepoch - e0);
+    const XSrc xe = d_x.offset((size_t)e0 * nsamp);
     double2* X = (double2*)ctx->X.p;
     RowRec64* rows = (RowRec64*)ctx->rows.p;
     const long rows_x = (long)ne * F * D * B;
-    if (rows_x * cols >= (1L << 31)) return set_error(ctx, GACQ_ERR_UNSUPPORTED, "verification engine: too many forward rows in one pass (lower the workspace limit)");
-    hipLaunchKernelGGL(mix64_kernel, dim3((unsigned)(rows_x * cols)), dim3(kBlock), 0, st, d_x.offset((size_t)e0 * nsamp), nsamp, X, (const double*)ctx->freq.p, tab, n,
-                       N, F * D, B, cols);
-    GACQ_HIP(ctx, hipGetLastError());
-    if ((rc = fft_exec(ctx, N, rows_x, false, X, true)) != GACQ_OK) return rc;
-    const long groups = (long)ne * P * D;
-    const size_t group_bytes = sizeof(double2) * (size_t)B * N;
-    long gc = (long)std::max<size_t>(1, std::min<size_t>((size_t)groups, ws_budget(ctx) / group_bytes));
-    gc = std::min<long>(gc, std::max<long>(1, ((1L << 31) - 1) / ((long)B * cols)));
-    if ((rc = ensure(ctx, ctx->Y, group_bytes * gc)) != GACQ_OK) return rc;
-    double2* Y = (double2*)ctx->Y.p;
-    for (long g0 = 0; g0 < groups; g0 += gc) {
-      const long ng = std::min(gc, groups - g0);
-      hipLaunchKernelGGL(conj_mul64_kernel, dim3((unsigned)(ng * B * cols)), dim3(kBlock), 0, st, (const double2*)X, (const double2*)sig->spectra64, Y,
-                         (const int*)ctx->items.p, (const int*)ctx->fset.p, g0, P, F, D, B, N, cols);
-      GACQ_HIP(ctx, hipGetLastError());
-      if ((rc = fft_exec(ctx, N, ng * B, true, Y, true)) != GACQ_OK) return rc;
-      hipLaunchKernelGGL(mag_peak64_kernel, dim3((unsigned)ng), dim3(kBlock), 0, st, (const double2*)Y, rows, g0, B, N, d_qrow);
-      GACQ_HIP(ctx, hipGetLastError());
+    switch (form) {
+      case Form::C128Fused4k:      // one kernel per search: the row never leaves the workgroup
+        rc = launch(6, fused4k_c128_kernel, 8 * (long)((ne + 7) / 8) * D * nchunk, kBlock, f64::kLdsBytes, xe, nsamp, C, d_items, d_freq, tab, tw, rows, ne, P, D, pch,
+                    nchunk);
+        break;
+      case Form::C128Lds4k:      // several blocks or carriers: forward spectra once, then one workgroup per (epoch, Doppler bin, item) over its B rows
+        rc = launch(0, c128_4k_forward_kernel, rows_x, kBlock, f64::kLdsBytes, xe, nsamp, X, d_freq, tab, tw, n, F * D, B);
+        if (rc == GACQ_OK)
+          rc = launch(6, c128_4k_correlate_kernel, 8 * (((long)ne * D + 7) / 8) * P, kBlock, f64::kLdsBytes, X, C, d_items, d_fset, tw, rows, ne, P, F, D, B);
+        break;
+      default: {      // the forms with a Z' round trip: carrier wipe-off, then the forward transform
+        if (rows_x * cols >= (1L << 31)) return set_error(ctx, GACQ_ERR_UNSUPPORTED, "%s: too many forward rows in one pass (lower the workspace limit)", what);
+        // split and radix-31: wipe-off into the correlation workspace (free until the first Z' pass), the outer DFT out of it into X
+        if (!rocfft && (rc = ensure(ctx, ctx->Y, x_epoch_bytes * ne)) != GACQ_OK) return rc;
+        double2* mixed = rocfft ? X : (double2*)ctx->Y.p;
+        rc = timed(ctx, stage(0), [&] {
+          int r = launch(-1, mix64_kernel, rows_x * cols, kBlock, 0, xe, nsamp, mixed, d_freq, tab, n, N, F * D, B, cols);
+          if (r == GACQ_OK && split) r = launch(-1, sk.forward, ((rows_x + 7) / 8) * 8 * R, kBlock, f64::kLdsBytes, mixed, X, tw, (unsigned)rows_x);
+          if (r == GACQ_OK && r31) r = launch(-1, c128_r31_forward_kernel, rows_x * chunksM, kBlock, 0, mixed, X, tw, M, chunksM);
+          return r;
+        });
+        if (rc == GACQ_OK && !split) rc = timed(ctx, stage(1), [&] { return fft_exec(ctx, M, rows_x * R, false, X, true); });
+      }
+    }
+    if (rc != GACQ_OK) return rc;
+    if (split || r31 || rocfft) {
+      // Z' passes of whole units of B rows each.  Split: an (epoch, Doppler bin) with its P items; radix-31 and rocFFT: an (epoch, item,
+      // Doppler bin) group.  Split and radix-31: at most 4 GiB a pass (or one unit / eight items' worth where that is more), as in the fp32
+      // split engines, and one unit a pass for a row dump; the rocFFT form fills the workspace.  No evening of the passes.
+      const long units = (long)ne * D * (split ? 1 : P);
+      const size_t unit_bytes = sizeof(double2) * (size_t)B * N * (split ? P : 1);
+      const size_t floor_bytes = split ? unit_bytes : 8 * unit_bytes * (size_t)D;
+      const size_t pass_cap = rocfft ? ws_budget(ctx) : std::min(ws_budget(ctx), std::max<size_t>((size_t)4 << 30, floor_bytes));
+      long uc = (long)std::max<size_t>(1, std::min<size_t>((size_t)units, pass_cap / unit_bytes));
+      uc = std::min<long>(uc, std::max<long>(1, ((1L << 31) - 1) / (split ? (long)B * R * nchunk : (long)B * cols)));      // the writer's grid below 2^31
+      if (d_qrow && !rocfft) uc = 1;
+      if ((rc = ensure(ctx, ctx->Y, unit_bytes * uc)) != GACQ_OK) return rc;
+      double2* Y = (double2*)ctx->Y.p;
+      for (long u0 = 0; u0 < units; u0 += uc) {
+        const long nu = std::min(uc, units - u0);
+        switch (form) {
+          case Form::C128Split:      // K2 + inner transforms + twiddle in one kernel; then outer inverse DFT-R + |.| + reduce
+            rc = launch(6, sk.corr, nu * B * nchunk * R, kBlock, f64::kLdsBytes, X, C, Y, d_items, d_fset, tw, u0, P, F, D, B, pch, nchunk);
+            if (rc == GACQ_OK) rc = launch(4, sk.reader, nu * P, kBlock, 0, Y, rows, u0, P, D, B, d_qrow);
+            break;
+          default:      // K2, rocFFT's inverse transforms of length M; then inverse DFT-31 + |.| + reduce, or magnitudes and peaks
+            rc = launch(2, conj_mul64_kernel, nu * B * cols, kBlock, 0, X, C, Y, d_items, d_fset, u0, P, F, D, B, N, cols);
+            if (rc == GACQ_OK) rc = timed(ctx, stage(3), [&] { return fft_exec(ctx, M, nu * B * R, true, Y, true); });
+            if (rc == GACQ_OK && r31) rc = launch(4, c128_r31_reader_kernel, nu, kBlock, 0, Y, rows, tw, u0, M, B, d_qrow);
+            if (rc == GACQ_OK && rocfft) rc = launch(4, mag_peak64_kernel, nu, kBlock, 0, Y, rows, u0, B, N, d_qrow);
+        }
+        if (rc != GACQ_OK) return rc;
+      }
     }
     const long nep = (long)ne * P;
-    hipLaunchKernelGGL(best_doppler64_kernel, dim3((unsigned)((nep + 63) / 64)), dim3(64), 0, st, (const RowRec64*)rows, d_out + (size_t)e0 * P, nep, D, N,
-                       sig->desc.metric_mode);
-    GACQ_HIP(ctx, hipGetLastError());
+    if ((rc = launch(5, best_doppler64_kernel, (nep + 63) / 64, 64, 0, rows, d_out + (size_t)e0 * P, nep, D, N, sig->desc.metric_mode)) != GACQ_OK) return rc;
   }
   return GACQ_OK;
 }
