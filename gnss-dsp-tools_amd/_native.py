@@ -261,6 +261,12 @@ SYMBOLS = {
     "gacq_stap_run_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                          ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gacq_stap_close": (None, [ctypes.c_void_p]),
+    # bearings from array covariances (bearing.py): the gacq_bearing_cfg, the two host tables, device pointers
+    "gacq_bearing_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong]),
+    "gacq_bearing_open": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "gacq_bearing_run_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p]),
+    "gacq_bearing_close": (None, [ctypes.c_void_p]),
     # navigation data (navdata.py): host arrays and the gacq_vit_job array as plain addresses
     "gacq_navsym_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

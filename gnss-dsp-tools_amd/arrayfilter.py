@@ -106,17 +106,23 @@ def auto_gain(tool, engine, firsts, opts, target_rms=TARGET_RMS):
 
 class Stream(streaming.Chunks):
     """Recordings fed piece by piece: feed(pieces) takes one piece per antenna (of equal length) and returns the outputs the pieces
-    complete; the concatenation of what the calls return is what one convert() of the whole recordings gives, and so are stats() and
-    the weights.  The tail kept on the device starts at the first input sample the next output's window needs."""
+    complete; the concatenation of what the calls return is what one convert() of the whole recordings gives, and so are stats(),
+    the weights and, with cov, the window sums.  The tail kept on the device starts at the first input sample the next output's window
+    needs."""
 
-    def __init__(self, tool, engine, M, gain, opts, dtype="int8", weights=False):
+    def __init__(self, tool, engine, M, gain, opts, dtype="int8", weights=False, cov=False):
         self.handle = tool.handle(engine, M, *opts)
-        self.engine, self.gain, self.dtype, self.weights = engine, float(gain), dtype, bool(weights)
+        self.engine, self.gain, self.dtype, self.weights, self.cov = engine, float(gain), dtype, bool(weights), bool(cov)
         self.traces = []             # weights: the weights, call by call
+        self.covs = []               # cov: the window sums of the owned blocks, call by call
         super().__init__(16, lambda in_first, in_count: tool.out_end(opts, in_first + in_count), self._run, lambda out: tool.first_needed(opts, out))
 
     def _run(self, ds, in_first, in_count, out_first, n_out, k):
-        got = self.handle.run(ds, in_first, out_first, n_out, self.gain, self.dtype, weights=self.weights)
+        got = self.handle.run(ds, in_first, out_first, n_out, self.gain, self.dtype, weights=self.weights, cov=self.cov)
+        if self.cov:
+            got, cv = got[:-1], got[-1]
+            got = got[0] if len(got) == 1 else got
+            self.covs.append(cv)
         if self.weights:
             got, w = got
             self.traces.append(w)
@@ -148,19 +154,24 @@ def lockstep(fins, piece_bytes=rawfile.PIECE_BYTES):
             return
 
 
-def convert_files(tool, engine, fins, fout, opts, gain=None, target_rms=TARGET_RMS, dtype="int8", ftrace=None, piece_bytes=rawfile.PIECE_BYTES):
+def convert_files(tool, engine, fins, fout, opts, gain=None, target_rms=TARGET_RMS, dtype="int8", ftrace=None, piece_bytes=rawfile.PIECE_BYTES,
+                  on_cov=None):
     """Read the open binary files fins in lockstep, piece by piece, and write the filtered recording to fout.  gain None: the automatic
     gain, that of the first 65536 outputs whatever the piece size (shorter pieces are read ahead until they hold its window).
-    (gain, samples written, clipped components)."""
+    on_cov(b, cov), if given, is called piece by piece with the int64 window sums of the blocks the piece's outputs own, the first of
+    them absolute block b (bearing.py).  (gain, samples written, clipped components)."""
     M = len(fins)
     st = None
     window_in = 0 if gain is not None else tool.auto_window(opts)
 
     def feed(ps):
+        first_owned = -(-st.next_out // st.handle.block)
         out = st.feed(ps)
         w = st.traces.pop()
         if ftrace is not None and w.numel():
             ftrace.write(w.cpu().numpy().tobytes())
+        if on_cov is not None:
+            on_cov(first_owned, st.covs.pop())
         return [out]
 
     def start(held):
@@ -170,7 +181,7 @@ def convert_files(tool, engine, fins, fout, opts, gain=None, target_rms=TARGET_R
         if gain is None:
             firsts = [np.concatenate([h[p] for h in held])[:2 * window_in] for p in range(M)]
             gain = auto_gain(tool, engine, firsts, opts, target_rms) if tool.out_end(opts, len(firsts[0]) // 2) > 0 else 1.0
-        st = Stream(tool, engine, M, gain, opts, dtype, weights=True)
+        st = Stream(tool, engine, M, gain, opts, dtype, weights=True, cov=on_cov is not None)
         return feed
 
     try:

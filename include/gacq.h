@@ -1030,6 +1030,52 @@ int gacq_stap_run_dev(gacq_stap* h, const void* const* d_in, long long in_first,
 void gacq_stap_close(gacq_stap* h);
 
 /* ---------------------------------------------------------------------------------------------
+ * Bearings of interferers (gacq_bearing.hip): the minimum-variance (Capon) spatial spectrum of every block's window covariance over a
+ * grid of directions, and the K strongest peaks that lie apart.  Every result is a function of (configuration, tables, covariance
+ * matrix) alone, so with gacq_null_run_dev's d_cov it is a function of the absolute block index.
+ * Input.  antennas = M in 2..8, load_shift in 0..40, cells = G in 1..32768, peaks = K in 1..4, cos_sep a finite double in -1..1.  Two
+ *    host tables, read by gacq_bearing_open (all trigonometry stays with the caller): a[g][p], the steering vector of cell g, complex
+ *    fp64 [G][M][2]; u[g], its direction, fp64 [G][3]; every entry finite.  R: int64 [..][M][M][2], both triangles, the layout of
+ *    gacq_null_run_dev's d_cov.  Evaluated block i < n takes row i stride of d_cov, stride >= 1.
+ * 1. Loading.  Step 3 of gacq_null: t = sum_p Re R[p][p];  d = (t >> load_shift) + 1;  A = R + d I, every entry converted to fp64.
+ * 2. Elimination.  For every cell g the elimination of gacq_null step 4 with b = a_g, in that order, every real product and sum
+ *    rounded on its own, nothing fused, the complex product and the division by the real pivot as written there:
+ *      for k = 0 .. M-1:  piv_k = Re A[k][k];  for r = k+1 .. M-1:  m = A[r][k] / piv_k;
+ *                            for q = k+1 .. M-1:  A[r][q] = A[r][q] - m A[k][q];      b[r] = b[r] - m b[k]
+ *    No back substitution.  (The matrix part does not depend on g.)
+ * 3. Quadratic form.  q_g = t_0 + t_1 + .. + t_(M-1), left to right, t_k = ((Re b_k)^2 + (Im b_k)^2) / piv_k: two products, one sum,
+ *    one division.  This is a_g^H A^-1 a_g; the Capon power 1 / q_g is left to the caller.
+ * 4. Eligibility.  A cell is eligible when q_g is finite and > 0.  floor = the largest eligible q_g, +inf when no cell is eligible.
+ * 5. Peaks, for k = 0 .. K-1.  g_k = the eligible, not yet excluded cell with the smallest q, ties to the lowest g; the record is
+ *    (int32 g_k, int32 0, double q).  Then every cell g with (u_g[0] u_gk[0] + u_g[1] u_gk[1]) + u_g[2] u_gk[2] >= cos_sep, evaluated
+ *    in that order, is excluded from the later ranks (g_k itself only if its own product reaches cos_sep: with cos_sep within a
+ *    rounding of |u|^2 a cell can take two ranks).  When no cell is left the record is (-1, 0, +inf).
+ * 6. Outputs, device memory on 8 bytes.  d_peaks: [n][K] records of 16 bytes; d_floor: double [n]; d_spectrum: NULL, or double [n][G]
+ *    holding q_g, ineligible values as computed, a NaN as the quiet NaN 0x7FF8000000000000 (IEEE 754 leaves the sign and the payload
+ *    of a computed NaN open).
+ * A value outside the ranges above, a table entry that is not finite, n below 0, stride below 1, n or stride or n stride above 2^48, a
+ * NULL d_cov, d_peaks or d_floor, a pointer off 8 bytes GACQ_ERR_BAD_ARG.  Everything is checked on the host before anything is
+ * launched; a refused call leaves every output untouched; n = 0 does nothing.
+ * gacq_bearing_check makes every check that needs no pointer, without a context.  gacq_bearing_open copies the tables to the device
+ * (planar) and allocates the workspace (it may wait for the device); gacq_bearing_run_dev is two launches (factors, spectrum and peaks)
+ * per chunk of at most min(2^14, 2^24 / G) blocks on the ctx stream, asynchronous, without state between calls and without host
+ * synchronisation.  The handle is closed before its context is destroyed.  tests/bearing_oracle.py restates the definition in numpy.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gacq_bearing_cfg {
+  int antennas;                    /* M, 2..8 */
+  int load_shift;                  /* diagonal loading d = (trace >> load_shift) + 1, 0..40 */
+  int cells;                       /* G, 1..32768 */
+  int peaks;                       /* K, 1..4 */
+  double cos_sep;                  /* cells whose direction cosine to a peak reaches this leave the later ranks; -1..1 */
+} gacq_bearing_cfg;
+typedef struct gacq_bearing gacq_bearing;
+
+int gacq_bearing_check(const gacq_bearing_cfg* cfg, long long n, long long stride);
+int gacq_bearing_open(gacq_ctx* ctx, const gacq_bearing_cfg* cfg, const double* a, const double* u, gacq_bearing** out);
+int gacq_bearing_run_dev(gacq_bearing* h, const void* d_cov, long long n, long long stride, void* d_peaks, void* d_floor, void* d_spectrum);
+void gacq_bearing_close(gacq_bearing* h);
+
+/* ---------------------------------------------------------------------------------------------
  * Navigation data from tracked prompts (gacq_navbits.hip; the framing is host code, gnss_dsp_tools_amd/navdata.py).
  *
  * gacq_navsym: symbol forming and bit synchronisation of K channels, one workgroup per channel.  Everything is host memory: the call
