@@ -244,6 +244,11 @@ SYMBOLS = {
     "gacq_cancel_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_void_p,
                                        ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # prompts across an antenna array (arrayprompt.py): cancel's arrays and the host array of device pointers
+    "gacq_aprompt_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_longlong, ctypes.c_longlong]),
+    "gacq_aprompt_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p]),
     # spatial nulling (nulling.py): the gacq_null_cfg and the host array of device pointers
     "gacq_null_tile": (ctypes.c_int, [ctypes.c_void_p]),
     "gacq_null_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_double,

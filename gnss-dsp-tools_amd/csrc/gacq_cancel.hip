@@ -17,45 +17,19 @@
 // samples mostly share a chip, and no per-tile staging pass is needed.
 // sin / cos: the quarter-turn reduction and polynomials of gacq_simulate.hip in a copy of their own (that file's bits stay what they
 // are).  The int8 output is rint / clamp of the very fp32 values the complex64 output stores.
+// The replica (cancel_sincos_turn, cancel_replica), the device tables CanSat / CanSeg and the host preparation of the segment table are
+// in gacq_cancelcore.h, which gacq_aprompt.hip shares: its prompts are cancel_project_kernel's amplitudes bit for bit.
 #pragma clang fp contract(off)
 
-#include "gacq_common.h"
+#include "gacq_cancelcore.h"
 #include "gacq_fft64.h"
-
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <vector>
 
 using namespace gacq;
 
 namespace {
 
-constexpr int kCanBlock = 256;
 constexpr int kCanRun = 8;                      // samples per lane: one 16-byte store of int8 I/Q
 constexpr int kCanTile = kCanBlock * kCanRun;
-constexpr int kCanMaxK = 32;
-constexpr int kCanMaxSegs = 1 << 20;
-constexpr long long kCanMaxN = 1ll << 24;
-constexpr int kCanMaxChips = 10240;             // the tracking loops' limit
-constexpr unsigned kCanMaxGrid = 1u << 16;      // workgroups; a longer call loops
-constexpr unsigned long long kCanTmbocMask = (1ull << 0) | (1ull << 4) | (1ull << 6) | (1ull << 29);
-
-struct CanSat {                                 // device form of a satellite
-  const uint8_t* chips;                         // L bytes, 0 / 1
-  double inv_l;
-  unsigned L, kind;
-  unsigned first, nseg;                         // its segments are segs[first .. first + nseg)
-};
-
-struct CanSeg {                                 // device form of a segment, 64 bytes
-  long long s0;
-  unsigned long long F, p0;                     // carrier step per sample and phase at s0, 2^-64 turn
-  unsigned long long cf_frac, frac0;            // code step per sample (fraction) and subchip fraction at s0, 2^-64 chip
-  unsigned n, cf_int, chip0;                    // samples; code step (whole chips, < 16); chip index at s0
-  float ar, ai;                                 // float32(A)
-  unsigned sat_touch;                           // satellite index | (touches the output range) << 8
-};
 
 struct CanArgs {
   const CanSat* sats;
@@ -76,60 +50,6 @@ struct CanProjArgs {
   long long in_first;
   unsigned nseg;
 };
-
-// (cos, sin) of 2 pi ph / 2^64
-__device__ __forceinline__ void cancel_sincos_turn(unsigned long long ph, float& c, float& s) {
-  const unsigned u = (unsigned)(ph >> 32) + 0x20000000u;          // + 1/8 turn: the quadrant index rounds to nearest
-  const unsigned q = u >> 30;
-  const float t = (float)((int)(u & 0x3fffffffu) - 0x20000000) * 9.31322574615478515625e-10f;      // quarter turns, [-1/2, 1/2)
-  const float t2 = t * t;
-  float ps = fmaf(t2, -4.602163099e-03f, 7.968021929e-02f);
-  ps = fmaf(ps, t2, -6.459634900e-01f);
-  ps = fmaf(ps, t2, 1.570796371e+00f) * t;
-  float pc = fmaf(t2, 9.036298725e-04f, -2.086007036e-02f);
-  pc = fmaf(pc, t2, 2.536692023e-01f);
-  pc = fmaf(pc, t2, -1.233700514e+00f);
-  pc = fmaf(pc, t2, 1.0f);
-  const float a = (q & 1u) ? ps : pc, b = (q & 1u) ? pc : ps;     // quarter turns: (c, s), (-s, c), (-c, -s), (s, -c)
-  c = __uint_as_float(__float_as_uint(a) ^ ((((q + 1u) >> 1) & 1u) << 31));
-  s = __uint_as_float(__float_as_uint(b) ^ (((q >> 1) & 1u) << 31));
-}
-
-// r = (rr, ri) and w of sample i = u of a segment.  (chip_at, cbit): the chip index whose byte the lane holds
-__device__ __forceinline__ void cancel_replica(const CanSat& s, const CanSeg& g, unsigned u, unsigned& chip_at, unsigned& cbit, float& rr, float& ri,
-                                               float& w) {
-  const unsigned long long th = g.p0 + (unsigned long long)u * g.F;
-  const unsigned long long lo = (unsigned long long)u * g.cf_frac, frac = g.frac0 + lo;
-  const unsigned ct = g.chip0 + u * g.cf_int + (unsigned)__umul64hi((unsigned long long)u, g.cf_frac) + (frac < lo ? 1u : 0u);      // < 2^29
-  unsigned chip = ct - (unsigned)((double)ct * s.inv_l) * s.L;
-  if ((int)chip < 0) chip += s.L;
-  if (chip >= s.L) chip -= s.L;
-  if (chip != chip_at) {
-    cbit = s.chips[chip];
-    chip_at = chip;
-  }
-  const unsigned b1 = (unsigned)(frac >> 63);
-  unsigned neg = cbit;
-  float mag = 1.0f;
-  if (s.kind == 1u) {
-    neg ^= b1;
-  } else if (s.kind == 2u || s.kind == 3u) {
-    const unsigned b6 = (unsigned)__umul64hi(frac, 12ull) & 1u;
-    if (s.kind == 2u) {
-      neg ^= b1;                                                  // w (c1 s1 + c6 s6) = w s1 (c1 +- c6)
-      mag = (b1 != b6) ? (float)(0.953463 - 0.301511) : (float)(0.953463 + 0.301511);
-    } else {
-      neg ^= ((kCanTmbocMask >> (chip % 33u)) & 1ull) ? b6 : b1;
-    }
-  } else if (s.kind >= 4u) {
-    if ((s.kind == 4u) != (b1 == 0u)) mag = 0.0f;
-  }
-  w = __uint_as_float(__float_as_uint(mag) ^ (neg << 31));
-  float c, sn;
-  cancel_sincos_turn(th, c, sn);
-  rr = w * c;
-  ri = w * sn;
-}
 
 template <bool INC>
 __global__ __launch_bounds__(kCanBlock) void cancel_project_kernel(const CanProjArgs a) {
@@ -326,22 +246,7 @@ __global__ __launch_bounds__(kCanBlock) void cancel_subtract_kernel(const CanArg
 
 }  // namespace
 
-#include "gacq_streamhost.h"
-
 namespace {
-
-// floor(frac(v) 2^64) mod 2^64, in IEEE double operations (as gacq_simulate.hip and tests/simulate_oracle.py have it)
-unsigned long long can_turns(double v) {
-  const double t = v - std::floor(v);                               // [0, 1]; 1 only when a tiny negative v rounds up
-  return t >= 1.0 ? 0ull : (unsigned long long)std::floor(std::ldexp(t, 64));
-}
-
-// whole part and floor(fraction 2^64) of v >= 0
-void can_fixed(double v, unsigned long long& whole, unsigned long long& frac) {
-  const double w = std::floor(v);
-  whole = (unsigned long long)w;
-  frac = (unsigned long long)std::floor(std::ldexp(v - w, 64));     // v - w is exact and below 1
-}
 
 bool can_touches(const gacq_cancel_seg& g, long long out_first, long long n_out) { return g.s0 < out_first + n_out && g.s0 + g.n > out_first; }
 
@@ -349,46 +254,12 @@ bool can_touches(const gacq_cancel_seg& g, long long out_first, long long n_out)
 int can_check(const gacq_cancel_sat* sats, int K, const gacq_cancel_seg* segs, double fs, int estimate, const void* d_in, int in_complex64,
               long long in_first, long long in_count, long long out_first, long long n_out, int out_complex64, const void* d_out, int* Ls) {
   if (!sats || !segs || !d_in || !d_out) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: NULL argument");
-  if (K < 1 || K > kCanMaxK) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: need 1 <= K <= %d satellites (K %d)", kCanMaxK, K);
-  if (!std::isfinite(fs) || !(fs > 0.0)) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: fs must be finite and positive");
+  if (const int rc = can_check_rate("gacq_cancel", K, fs)) return rc;
   if (const int rc = st_check_range(nullptr, "gacq_cancel", in_first, in_count, out_first, n_out)) return rc;
   if (in_complex64 && (uintptr_t)d_in % 8u) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: complex64 input must be 8-byte aligned");
   if (out_complex64 && (uintptr_t)d_out % 8u) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: complex64 output must be 8-byte aligned");
   long long total = 0;
-  for (int k = 0; k < K; k++) {
-    const gacq_cancel_sat& s = sats[k];
-    if (!s.code) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: satellite %d has no code", k);
-    const int L = gacq_code_length(s.code);
-    if (L < 0) return set_error(nullptr, GACQ_ERR_UNKNOWN_CODE, "gacq_cancel: satellite %d: unknown code '%s'", k, s.code);
-    if (L > kCanMaxChips)
-      return set_error(nullptr, GACQ_ERR_UNSUPPORTED, "gacq_cancel: satellite %d: '%s' has %d chips, more than the %d served", k, s.code, L, kCanMaxChips);
-    if (Ls) Ls[k] = L;
-    std::vector<uint8_t> chips(L);
-    const int rc = gacq_code_chips(s.code, s.prn, chips.data(), L);
-    if (rc < 0) return set_error(nullptr, rc, "gacq_cancel: satellite %d: no PRN %d in '%s'", k, s.prn, s.code);
-    if (s.kind < 0 || s.kind > 5) return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: satellite %d: kind %d outside 0..5", k, s.kind);
-    if (s.nseg < 0 || s.nseg > kCanMaxSegs || (total += s.nseg) > kCanMaxSegs)
-      return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: satellite %d: need 0 <= nseg and at most %d segments in all", k, kCanMaxSegs);
-  }
-  const gacq_cancel_seg* g = segs;
-  for (int k = 0; k < K; k++) {
-    const int L = gacq_code_length(sats[k].code);
-    for (int i = 0; i < sats[k].nseg; i++, g++) {
-      if (!std::isfinite(g->carrier_hz) || !std::isfinite(g->carrier_phase) || !std::isfinite(g->code_rate_hz) || !std::isfinite(g->code_phase) ||
-          !std::isfinite(g->amp_re) || !std::isfinite(g->amp_im))
-        return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: satellite %d, segment %d: a parameter is not finite", k, i);
-      if (g->n < 1 || g->n > kCanMaxN || g->s0 < 0 || g->s0 > kStreamMaxIndex - g->n)
-        return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: satellite %d, segment %d: need 1 <= n <= 2^24, s0 >= 0 and s0 + n <= 2^48 (s0 %lld, n %lld)",
-                         k, i, g->s0, g->n);
-      if (!(g->code_rate_hz > 0.0) || !(g->code_rate_hz / fs < 16.0))
-        return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: satellite %d, segment %d: need 0 < code rate / fs < 16 (%g / %g)", k, i, g->code_rate_hz, fs);
-      if (!(g->code_phase >= 0.0 && g->code_phase < (double)L))
-        return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: satellite %d, segment %d: code phase %g outside [0, %d)", k, i, g->code_phase, L);
-      if (i > 0 && g->s0 < g[-1].s0 + g[-1].n)
-        return set_error(nullptr, GACQ_ERR_BAD_ARG, "gacq_cancel: satellite %d: segment %d (from %lld) starts before segment %d ends (%lld)", k, i, g->s0,
-                         i - 1, g[-1].s0 + g[-1].n);
-    }
-  }
+  if (const int rc = can_check_table("gacq_cancel", sats, K, segs, fs, true, Ls, &total)) return rc;
   if (n_out == 0) return GACQ_OK;
   if (out_first < in_first || out_first + n_out > in_first + in_count)
     return set_error(nullptr, GACQ_ERR_SHORT_INPUT, "gacq_cancel: outputs %lld .. %lld need their inputs, present are %lld .. %lld", out_first,
@@ -418,51 +289,16 @@ extern "C" int gacq_cancel_dev(gacq_ctx* ctx, const gacq_cancel_sat* sats, int K
   int rc = can_check(sats, K, segs, fs, estimate, d_in, in_complex64, in_first, in_count, out_first, n_out, out_complex64, d_out, Ls);
   if (rc < 0) return st_forward(ctx, rc);
   if (n_out == 0) return GACQ_OK;
-  std::vector<ChipTable> tabs(K);
-  for (int k = 0; k < K; k++)
-    if ((rc = chip_table_host(ctx, sats[k].code, sats[k].prn, Ls[k], true, tabs[k])) < 0)
-      return set_error(ctx, rc, "gacq_cancel_dev: satellite %d: no PRN %d in '%s'", k, sats[k].prn, sats[k].code);
-  size_t S = 0;
-  for (int k = 0; k < K; k++) S += (size_t)sats[k].nseg;
-  std::vector<CanSat> hs(K);
-  std::vector<CanSeg> hg(std::max<size_t>(S, 1));
-  bool any = false;
   GACQ_DEVICE(ctx);
   hipStream_t stream = ctx->stream;
-  size_t at = 0;
-  for (int k = 0; k < K; k++) {
-    CanSat& t = hs[k];
-    if ((rc = chip_table_dev(ctx, tabs[k], &t.chips)) != GACQ_OK) return rc;
-    t.L = (unsigned)Ls[k];
-    t.inv_l = 1.0 / (double)Ls[k];
-    t.kind = (unsigned)sats[k].kind;
-    t.first = (unsigned)at;
-    t.nseg = (unsigned)sats[k].nseg;
-    for (int i = 0; i < sats[k].nseg; i++, at++) {
-      const gacq_cancel_seg& g = segs[at];
-      CanSeg& d = hg[at];
-      std::memset(&d, 0, sizeof(d));
-      d.s0 = g.s0;
-      d.n = (unsigned)g.n;
-      d.F = can_turns(g.carrier_hz / fs);
-      d.p0 = can_turns(g.carrier_phase);
-      unsigned long long ci, cw;
-      can_fixed(g.code_rate_hz / fs, ci, d.cf_frac);
-      d.cf_int = (unsigned)ci;
-      can_fixed(g.code_phase, cw, d.frac0);
-      d.chip0 = (unsigned)cw;
-      d.ar = (float)g.amp_re;
-      d.ai = (float)g.amp_im;
-      const bool touch = can_touches(g, out_first, n_out);
-      any = any || touch;
-      d.sat_touch = (unsigned)k | (touch ? 1u << 8 : 0u);
-    }
-  }
-  DevBuf& d_sats = ctx->tables["cancel:sats"];
-  DevBuf& d_segs = ctx->tables["cancel:segs"];
+  CanTable tab;
+  if ((rc = can_table_build(ctx, "gacq_cancel_dev", sats, K, segs, Ls, fs, [&](const gacq_cancel_seg& g) { return can_touches(g, out_first, n_out); },
+                            tab)) != GACQ_OK)
+    return rc;
+  const size_t S = tab.S;
+  const bool any = tab.any;
+  const std::vector<CanSeg>& hg = tab.segs;
   DevBuf& d_amps = ctx->tables["cancel:amps"];
-  if ((rc = ensure(ctx, d_sats, sizeof(CanSat) * kCanMaxK)) != GACQ_OK) return rc;
-  if ((rc = ensure(ctx, d_segs, sizeof(CanSeg) * hg.size())) != GACQ_OK) return rc;
   if ((rc = ensure(ctx, d_amps, sizeof(double2) * hg.size() + 8)) != GACQ_OK) return rc;
   unsigned long long* d_clip = (unsigned long long*)((double2*)d_amps.p + hg.size());
   // the uploads come from pageable memory and the downloads go to it: the stream is waited for on every way out from here on
@@ -470,14 +306,13 @@ extern "C" int gacq_cancel_dev(gacq_ctx* ctx, const gacq_cancel_sat* sats, int K
   std::vector<double2> ha(amps_out && estimate && any ? S : 0);
   unsigned long long nclip = 0;
   const auto queue = [&]() -> hipError_t {
-    hipError_t e = hipMemcpyAsync(d_sats.p, hs.data(), sizeof(CanSat) * (size_t)K, hipMemcpyHostToDevice, stream);
+    hipError_t e = can_table_queue(tab, stream);
     if (e != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(d_segs.p, hg.data(), sizeof(CanSeg) * hg.size(), hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(d_clip, 0, 8, stream)) != hipSuccess) return e;
     if (estimate && any) {
       CanProjArgs p;
-      p.sats = (const CanSat*)d_sats.p;
-      p.segs = (CanSeg*)d_segs.p;
+      p.sats = tab.d_sats;
+      p.segs = tab.d_segs;
       p.amps = (double2*)d_amps.p;
       p.in = d_in;
       p.in_first = in_first;
@@ -488,8 +323,8 @@ extern "C" int gacq_cancel_dev(gacq_ctx* ctx, const gacq_cancel_sat* sats, int K
       if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     CanArgs a;
-    a.sats = (const CanSat*)d_sats.p;
-    a.segs = (const CanSeg*)d_segs.p;
+    a.sats = tab.d_sats;
+    a.segs = tab.d_segs;
     a.in = (const unsigned char*)d_in + (size_t)(out_first - in_first) * esz;
     a.out = d_out;
     a.clip = d_clip;

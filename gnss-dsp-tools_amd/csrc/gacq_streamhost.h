@@ -1,8 +1,8 @@
-// Host side of the recording converters, shared by gacq_ingest.hip, gacq_mitigate.hip, gacq_ddc.hip, gacq_requant.hip, gacq_cancel.hip,
-// gacq_null.hip and gacq_stap.hip (the last two through gacq_arrayhost.h): the checks every "absolute sample index in, absolute sample
-// index out" entry point makes in the same words, the status of a launch, and the device block of an open handle.  Host code only; each
-// file includes it after its kernels.  `who` is the entry point's name as its messages carry it; `ctx` is the context the message goes
-// to, nullptr from a gacq_*_check.
+// Host side of the recording converters, shared by gacq_ingest.hip, gacq_mitigate.hip, gacq_ddc.hip, gacq_requant.hip, gacq_cancel.hip
+// and gacq_aprompt.hip (these two through gacq_cancelcore.h), gacq_null.hip and gacq_stap.hip (through gacq_arrayhost.h): the checks
+// every "absolute sample index in, absolute sample index out" entry point makes in the same words, the status of a launch, and the
+// device block of an open handle.  Host code only.  `who` is the entry point's name as its messages carry it; `ctx` is the context
+// the message goes to, nullptr from a gacq_*_check.
 #pragma once
 
 #include "gacq_common.h"

@@ -884,6 +884,23 @@ void gacq_requant_close(gacq_requant* h);
  * GACQ_ERR_UNSUPPORTED; an output sample whose input is not present, or with estimate a segment that touches the output range and does
  * not lie wholly inside the input, GACQ_ERR_SHORT_INPUT.  A refused call leaves d_out untouched; n_out = 0 does nothing.  Up to two
  * launches on the ctx stream; the call returns when the results are there.
+ * Prompts across an antenna array (gacq_aprompt.hip, gacq_aprompt_dev): the estimate alone, of M recordings on one sample clock against
+ * the same satellites and segments.  antennas = M in 1..8; d_in is a host array of M device pointers, row p holding input samples
+ * in_first .. in_first + in_count - 1 of antenna p, interleaved int8 I/Q at any byte address or complex64 8-byte aligned (the
+ * convention of gacq_null_run_dev; two antennas may share a pointer).  amp_re and amp_im are not looked at.  For every segment that
+ * lies wholly inside the input range and every antenna p
+ *     C_p = sum_j x_p(j) conj(r(j)),   E = sum_j w(pos(j))^2,   A_p = C_p / E (0 when E = 0)
+ *   with the operations of the estimate above: the same fixed-point phase and code position, the same fp32 products each rounded on
+ *   its own, the same order of the fp64 sums (sample i of the segment to lane i mod 256, a lane adds in ascending i, lanes by DPP row
+ *   sums and a fixed LDS tree).  A_p is bit for bit the A that gacq_cancel_dev (estimate) returns for that segment on antenna p's
+ *   recording alone: the bits depend on the segment and its own samples, not on M, the other antennas, the call, the other segments
+ *   or the addresses.  The replica of a sample is built once for all M antennas.
+ * prompts_out (host): complex fp64 [segment][antenna][2]; energy_out (host, or NULL): E, fp64 [segment].  A segment that is not wholly
+ * inside the input is left untouched in both (callers prefill, e.g. with NaN): no error, and nothing outside the rows is read.
+ * Limits and checks are those above, and antennas outside 1..8, a NULL row, a complex64 row off 8 bytes, a NULL prompts_out
+ * GACQ_ERR_BAD_ARG (gacq_aprompt_check makes the checks that need no context).  A refused call launches nothing and writes nothing.
+ * One launch on the ctx stream; the call returns when the results are there.
+ * The replica, the device tables and the host preparation of both entry points are csrc/gacq_cancelcore.h.
  * ------------------------------------------------------------------------------------------- */
 typedef struct gacq_cancel_sat {
   const char* code;                /* code module, e.g. "gps.ca" */
@@ -907,6 +924,10 @@ int gacq_cancel_check(const gacq_cancel_sat* sats, int K, const gacq_cancel_seg*
 int gacq_cancel_dev(gacq_ctx* ctx, const gacq_cancel_sat* sats, int K, const gacq_cancel_seg* segs, double fs, int estimate, const void* d_in,
                     int in_complex64, long long in_first, long long in_count, long long out_first, long long n_out, int out_complex64, void* d_out,
                     double* amps_out, unsigned long long* clipped);
+int gacq_aprompt_check(const gacq_cancel_sat* sats, int K, const gacq_cancel_seg* segs, double fs, const void* const* d_in, int antennas,
+                       int in_complex64, long long in_first, long long in_count);
+int gacq_aprompt_dev(gacq_ctx* ctx, const gacq_cancel_sat* sats, int K, const gacq_cancel_seg* segs, double fs, const void* const* d_in,
+                     int antennas, int in_complex64, long long in_first, long long in_count, double* prompts_out, double* energy_out);
 
 /* ---------------------------------------------------------------------------------------------
  * Spatial nulling with an antenna array (gacq_null.hip): M recordings on one sample clock in, one recording out, under weights that
