@@ -266,6 +266,14 @@ SYMBOLS = {
     "gacq_stap_run_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                          ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gacq_stap_close": (None, [ctypes.c_void_p]),
+    # per-satellite beams (beams.py): the gacq_beams_cfg, the host arrays of K gains and of K output pointers
+    "gacq_beams_tile": (ctypes.c_int, [ctypes.c_void_p]),
+    "gacq_beams_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p,
+                                        ctypes.c_int]),
+    "gacq_beams_open": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "gacq_beams_run_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                                          ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gacq_beams_close": (None, [ctypes.c_void_p]),
     # bearings from array covariances (bearing.py): the gacq_bearing_cfg, the two host tables, device pointers
     "gacq_bearing_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong]),
     "gacq_bearing_open": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),

@@ -1,4 +1,4 @@
-// What the antenna-array kernels share (gacq_null.hip, gacq_stap.hip): the bounds and the launch constants, the 16-byte load at any
+// What the antenna-array kernels share (gacq_null.hip, gacq_stap.hip, gacq_beams.hip): the bounds and the launch constants, the 16-byte load at any
 // address, the weight quantiser, the byte selects of a covariance fragment and the output epilogue of the apply kernels.  Both files
 // begin with `#pragma clang fp contract(off)` ahead of every include, and this header relies on it: what is here keeps the operations,
 // and so the bits and the instructions, it had when each file held its own copy.
@@ -11,10 +11,19 @@
 
 #include <cmath>
 
+namespace gacq {
+
+// null_cov_kernel, which lives in gacq_null.hip alone, launched for another file of the library: C_b of the nblk blocks of Lb samples
+// that begin at in[p] (kArMaxM device pointers, the slots from M up any valid one), into C [block][8][8][2]
+void null_launch_cov(const uint8_t* const* in, int* C, long long nblk, int Lb, int M, hipStream_t stream);
+
+}  // namespace gacq
+
 namespace {
 
 constexpr int kArBlock = 256;                        // threads a workgroup
 constexpr int kArMaxM = 8, kArMaxWindow = 64, kArMaxLb = 32768, kArMaxShift = 40;
+constexpr int kArMaxBeams = 16;                      // outputs of one gacq_beams call
 constexpr long long kArMaxChunk = 1ll << 14;         // blocks whose outputs one triple of launches writes, at most (2^29 samples)
 constexpr int kArRuns = 8;                           // runs a lane works through
 constexpr int kArTile = kArBlock * kArRuns * 8;      // 16384 samples a workgroup

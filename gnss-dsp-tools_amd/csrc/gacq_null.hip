@@ -101,6 +101,22 @@ __global__ __launch_bounds__(kArBlock, 2) void null_cov_kernel(const NlCovArgs a
   }
 }
 
+}  // namespace
+
+void gacq::null_launch_cov(const uint8_t* const* in, int* C, long long nblk, int Lb, int M, hipStream_t stream) {
+  NlCovArgs cv;
+  for (int p = 0; p < kArMaxM; p++) cv.in[p] = in[p];
+  cv.C = C;
+  cv.nblk = nblk;
+  cv.Lb = Lb;
+  cv.M = M;
+  cv.wpb_log2 = Lb >= 256 ? 2 : Lb >= 128 ? 1 : 0;
+  const long long per = (kArBlock / 64) >> cv.wpb_log2, npass = (cv.nblk + per - 1) / per;
+  hipLaunchKernelGGL(null_cov_kernel, dim3((unsigned)std::min<long long>(npass, (long long)kArMaxGrid)), dim3(kArBlock), 0, stream, cv);
+}
+
+namespace {
+
 // ---- weights
 
 struct NlWgtArgs {
@@ -292,15 +308,9 @@ extern "C" int gacq_null_run_dev(gacq_null* h, const void* const* d_in, long lon
       "gacq_null_run_dev", *h, gacq_null_check, ArRun{d_in, in_first, in_count, out_first, n_out, gain, out_complex64, d_out, d_stats, d_weights, d_cov},
       kArMaxChunk, (size_t)(kArMaxChunk + kArMaxWindow) * 128,
       [&](const ArRun& r) {
-        NlCovArgs cv;
-        ar_inputs(cv.in, r, c.antennas, r.pb0 * c.block);
-        cv.C = r.dC;
-        cv.nblk = r.ncov;
-        cv.Lb = c.block;
-        cv.M = c.antennas;
-        cv.wpb_log2 = c.block >= 256 ? 2 : c.block >= 128 ? 1 : 0;
-        const long long per = (kArBlock / 64) >> cv.wpb_log2, npass = (cv.nblk + per - 1) / per;
-        hipLaunchKernelGGL(null_cov_kernel, dim3((unsigned)std::min<long long>(npass, (long long)kArMaxGrid)), dim3(kArBlock), 0, stream, cv);
+        const uint8_t* in[kArMaxM];
+        ar_inputs(in, r, c.antennas, r.pb0 * c.block);
+        null_launch_cov(in, r.dC, r.ncov, c.block, c.antennas, stream);
       },
       [&](const ArRun& r) {
         NlWgtArgs wg;

@@ -35,7 +35,8 @@ class Chunks:
     the bytes of a sample that a chunk cut.  A tool says how many bits an input sample takes and hands in three callables:
         supported(in_first, in_count)  the end of the outputs that inputs in_first .. in_first + in_count - 1 support (per output)
         launch(ds, in_first, in_count, out_first, n_out, k)  output k's samples out_first .. out_first + n_out - 1 from the whole
-                                       samples ds, one flat tensor of bytes per input; what it returns is what feed returns
+                                       samples ds, one flat tensor of bytes per input; what it returns is what feed returns -- for
+                                       outputs that share one index range (beams) a list, one tensor per output, under one k
         needed(next_out)               the first input sample that the outputs from next_out on still need; for samples of less
                                        than a byte, on a byte boundary
     Any device's tensors will do: the machine only joins, cuts and clones them."""
@@ -97,9 +98,9 @@ class Handle:
         h = ctypes.c_void_p()
         nat.check(opener(engine._ctx, *args, ctypes.byref(h)), engine._ctx)
         self._h = h
-        if stats:
+        if stats:                                    # True: the two counters most tools keep; a number: that many
             torch = nat.require_torch()
-            self._stats = torch.zeros(2, dtype=torch.int64, device="cuda:%d" % engine.device)
+            self._stats = torch.zeros(2 if stats is True else int(stats), dtype=torch.int64, device="cuda:%d" % engine.device)
         engine._live.add(self)
 
     def _check_open(self):

@@ -1051,6 +1051,51 @@ int gacq_stap_run_dev(gacq_stap* h, const void* const* d_in, long long in_first,
 void gacq_stap_close(gacq_stap* h);
 
 /* ---------------------------------------------------------------------------------------------
+ * Per-satellite beams (gacq_beams.hip): gacq_null with K constraints at once.  M recordings in, K recordings out; output k is formed
+ * under the block-wise minimum-power weights of constraint c_k (an MVDR beam toward the steering vector c_k, as arrayprompt measures
+ * it).  The block covariance, the window and the loading do not depend on the constraint and are formed once for all K.
+ * Input.  antennas = M in 2..8 and d_in as gacq_null; beams = K in 1..16; c[k] = (re, im) of the M entries of c_k, every c_k finite
+ *    and not all zero; entries past M and rows past K are ignored.
+ * 1.-3. Block covariance, window, loading.  Steps 1 to 3 of gacq_null, unchanged: C_b, R_b, A = R_b + d I.
+ * 4.-7. For every beam k < K: steps 4 to 7 of gacq_null with c = c_k and gain = gain[k]: the weights, the quantised weights, the
+ *    apply and the output d_out[k].
+ * Contract.  Every byte of output k, its quantised weights and its clip count are bit for bit what gacq_null_run_dev writes for the
+ *    same inputs and call range under constraint c_k and gain gain[k], whatever K, the other beams, their order and the output
+ *    addresses are: the elimination of A never reads the right-hand side, and every operation on b in step 4 depends only on A's
+ *    multipliers m = A[r][k] / piv_k, its pivots and b itself, so the forward pass on b_k after the elimination, with m formed again
+ *    by the same division, gives the bits of the fused loop.
+ * 8. Side outputs, each NULL or device memory.  d_stats: K + 1 uint64 that the caller zeroed, 8-byte aligned: [k] the components of
+ *    int8 output k that the clip changed, [K] the owned blocks.  d_weights: int32 [owned block][K][M][2].  d_cov: gacq_null's, int64
+ *    [owned block][M][M][2], independent of the beams.
+ * gain is a host array of K doubles and d_out a host array of K device pointers, each at any byte address (complex64: on 8 bytes).
+ * Outputs that overlap each other or an input are the caller's business: nothing is checked and the bytes of the overlap are
+ * undefined.  The support rule, the limits and the alignment rules are those of gacq_null.  GACQ_ERR_BAD_ARG for everything
+ * gacq_null refuses and for beams outside 1..16 (checked after the antennas), a c_k that is not finite or all zero (the message
+ * names k), a gain[k] that is not finite and positive, a NULL gain, d_out or entry of d_out, a complex64 d_out[k] off 8 bytes.
+ * Everything is checked on the host before anything is launched; a refused call leaves every output untouched; n_out = 0 does
+ * nothing.  gacq_beams_check, gacq_beams_open (which also puts the constraints on the device), gacq_beams_close and gacq_beams_tile
+ * are what their gacq_null counterparts are; gacq_beams_run_dev is three launches (block covariances -- gacq_null's own kernel --,
+ * the weights of all beams, all outputs) per 2^14 blocks on the ctx stream.  The host path is csrc/gacq_arrayhost.h.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gacq_beams_cfg {
+  int antennas;                    /* M, 2..8 */
+  int beams;                       /* K, 1..16 */
+  int block;                       /* Lb: samples per covariance block, a multiple of 64 in 64..32768 */
+  int window;                      /* W: blocks the covariance sums over, 1..64 */
+  int load_shift;                  /* diagonal loading d = (trace >> load_shift) + 1, 0..40 */
+  double c[16][16];                /* row k: re, im of the M entries of c_k; the rest is ignored */
+} gacq_beams_cfg;
+typedef struct gacq_beams gacq_beams;
+
+int gacq_beams_tile(const gacq_beams_cfg* cfg);
+int gacq_beams_check(const gacq_beams_cfg* cfg, long long in_first, long long in_count, long long out_first, long long n_out,
+                     const double* gain, int out_complex64);
+int gacq_beams_open(gacq_ctx* ctx, const gacq_beams_cfg* cfg, gacq_beams** out);
+int gacq_beams_run_dev(gacq_beams* h, const void* const* d_in, long long in_first, long long in_count, long long out_first, long long n_out,
+                       const double* gain, int out_complex64, void* const* d_out, void* d_stats, void* d_weights, void* d_cov);
+void gacq_beams_close(gacq_beams* h);
+
+/* ---------------------------------------------------------------------------------------------
  * Bearings of interferers (gacq_bearing.hip): the minimum-variance (Capon) spatial spectrum of every block's window covariance over a
  * grid of directions, and the K strongest peaks that lie apart.  Every result is a function of (configuration, tables, covariance
  * matrix) alone, so with gacq_null_run_dev's d_cov it is a function of the absolute block index.
