@@ -49,14 +49,10 @@ __global__ __launch_bounds__(kArBlock) void beams_weights_kernel(const BmWgtArgs
   if (i >= a.nblk) return;
   const int r = lane >> 3, c = lane & 7, M = a.M, K = a.K;
   const bool in = r < M && c < M;
-  // ---- the window sum
+  // ---- the window sum, the loading and the elimination of A alone: nulling's own (gacq_arraycore.h)
   const int* pc = a.C + ((long long)(i >= a.warm ? a.p_off + i - a.W : 0) * 64 + lane) * 2;
-  long long Rre = 0, Rim = 0;
-  for (int j = 0; j < a.W; j++) {
-    const int2 v = *reinterpret_cast<const int2*>(pc + 128 * (long long)j);
-    Rre += v.x;
-    Rim += v.y;
-  }
+  long long Rre, Rim;
+  ar_window_sum(pc, a.W, Rre, Rim);
   const long long b = a.b_first + i;
   const bool owned = b >= a.own_first;
   if (owned && a.cov && in) {
@@ -64,22 +60,9 @@ __global__ __launch_bounds__(kArBlock) void beams_weights_kernel(const BmWgtArgs
     o[0] = Rre;
     o[1] = Rim;
   }
-  // ---- the loading
-  long long t = 0;
-  for (int p = 0; p < M; p++) t += __shfl(Rre, 9 * p, 64);
-  const long long d = (t >> a.shift) + 1;
-  double Are = in ? (double)(Rre + (r == c ? d : 0)) : 0.0, Aim = in ? (double)Rim : 0.0;
-  // ---- elimination of A alone: A[r][c] -= m A[k][c] with m = A[r][k] / piv, for r > k
-  for (int k = 0; k < M; k++) {
-    const double piv = __shfl(Are, 9 * k, 64);
-    const double lre = __shfl(Are, 8 * r + k, 64), lim = __shfl(Aim, 8 * r + k, 64);
-    const double ure = __shfl(Are, 8 * k + c, 64), uim = __shfl(Aim, 8 * k + c, 64);
-    if (r > k && r < M && c > k && c < M) {
-      const double mre = lre / piv, mim = lim / piv;
-      Are = Are - (mre * ure - mim * uim);
-      Aim = Aim - (mre * uim + mim * ure);
-    }
-  }
+  double Are, Aim;
+  ar_load_diagonal(Rre, Rim, a.shift, M, r, c, Are, Aim);
+  ar_eliminate(Are, Aim, M, r, c);
   // ---- the right-hand sides, eight beams at a time: the lane's column is beam 8 g + c
   for (int g = 0; 8 * g < K; g++) {
     const int beam = 8 * g + c;

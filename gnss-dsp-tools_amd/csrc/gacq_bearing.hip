@@ -5,8 +5,10 @@
 //
 // Two launches per chunk of blocks, on one stream:
 //   bearing_factor_kernel    a wave per block, lane 8 r + c holds A[r][c] as in null_weights_kernel: the loading and the elimination of
-//      the matrix in the order of the header.  What a cell needs of it goes to the workspace, 64 pairs of doubles a block: the
-//      multiplier m = A[r][k] / piv_k at [r][k], r > k, and (piv_k, 0) at [k][k].  None of that depends on the cell.
+//      the matrix are that kernel's own functions (ar_load_diagonal, ar_eliminate of gacq_arraycore.h, which also holds the bounds on
+//      the antennas and the shift), so the matrix factored here is the matrix nulling solves.  What a cell needs of it goes to the
+//      workspace, 64 pairs of doubles a block: the multiplier m = A[r][k] / piv_k at [r][k], r > k, and (piv_k, 0) at [k][k].  None of
+//      that depends on the cell.
 //   bearing_spectrum_kernel  one workgroup of 256 lanes per block; lane t owns the cells g = t, t + 256, ..  The block's factor is read
 //      once into 1 KB of LDS and every use is a broadcast read; a_g comes from the planar copy [p][re|im][g] of the table that
 //      gacq_bearing_open made, so a wave reads 512 consecutive bytes per component; b stays in registers (the antennas are a
@@ -22,7 +24,7 @@
 //      any order.
 #pragma clang fp contract(off)
 
-#include "gacq_common.h"
+#include "gacq_arraycore.h"
 
 #include <algorithm>
 #include <cmath>
@@ -33,7 +35,7 @@ using namespace gacq;
 namespace {
 
 constexpr int kBrBlock = 256;                        // threads a workgroup
-constexpr int kBrMaxM = 8, kBrMinM = 2, kBrMaxShift = 40, kBrMaxCells = 32768, kBrMaxPeaks = 4;
+constexpr int kBrMinM = 2, kBrMaxCells = 32768, kBrMaxPeaks = 4;      // at most kArMaxM antennas, load_shift at most kArMaxShift
 constexpr long long kBrMaxChunk = 1ll << 14;         // blocks a pair of launches evaluates, at most
 constexpr long long kBrRowDoubles = 1ll << 24;       // doubles of the q rows of a chunk, at most (128 MiB)
 constexpr long long kBrMaxIndex = 1ll << 48;
@@ -58,23 +60,11 @@ __global__ __launch_bounds__(kBrBlock) void bearing_factor_kernel(const BrFactor
     Rre = pr[0];
     Rim = pr[1];
   }
-  // ---- the loading
-  long long t = 0;
-  for (int p = 0; p < M; p++) t += __shfl(Rre, 9 * p, 64);
-  const long long d = (t >> a.shift) + 1;
-  double Are = in ? (double)(Rre + (r == c ? d : 0)) : 0.0, Aim = in ? (double)Rim : 0.0;
-  // ---- elimination: A[r][c] -= m A[k][c] with m = A[r][k] / piv, for r > k, c > k; a lane below the diagonal is left with A[r][c] as
-  // step c finds it, the numerator of its multiplier
-  for (int k = 0; k < M; k++) {
-    const double piv = __shfl(Are, 9 * k, 64);
-    const double lre = __shfl(Are, 8 * r + k, 64), lim = __shfl(Aim, 8 * r + k, 64);
-    const double ure = __shfl(Are, 8 * k + c, 64), uim = __shfl(Aim, 8 * k + c, 64);
-    if (r > k && r < M && c > k && c < M) {
-      const double mre = lre / piv, mim = lim / piv;
-      Are = Are - (mre * ure - mim * uim);
-      Aim = Aim - (mre * uim + mim * ure);
-    }
-  }
+  // ---- the loading and the elimination of nulling (gacq_arraycore.h); a lane below the diagonal is left with the numerator of its
+  // multiplier
+  double Are, Aim;
+  ar_load_diagonal(Rre, Rim, a.shift, M, r, c, Are, Aim);
+  ar_eliminate(Are, Aim, M, r, c);
   const double piv = __shfl(Are, 9 * c, 64);          // of the lane's column
   double2 f = make_double2(0.0, 0.0);
   if (in && r > c) f = make_double2(Are / piv, Aim / piv);
@@ -231,10 +221,10 @@ struct gacq_bearing {
 static int check_cfg(const gacq_bearing_cfg* c) {
   const char* who = "gacq_bearing";
   if (!c) return gacq::set_error(nullptr, GACQ_ERR_BAD_ARG, "%s: NULL argument", who);
-  if (c->antennas < kBrMinM || c->antennas > kBrMaxM)
-    return gacq::set_error(nullptr, GACQ_ERR_BAD_ARG, "%s: %d antennas: need %d..%d", who, c->antennas, kBrMinM, kBrMaxM);
-  if (c->load_shift < 0 || c->load_shift > kBrMaxShift)
-    return gacq::set_error(nullptr, GACQ_ERR_BAD_ARG, "%s: load_shift %d lies outside 0..%d", who, c->load_shift, kBrMaxShift);
+  if (c->antennas < kBrMinM || c->antennas > kArMaxM)
+    return gacq::set_error(nullptr, GACQ_ERR_BAD_ARG, "%s: %d antennas: need %d..%d", who, c->antennas, kBrMinM, kArMaxM);
+  if (c->load_shift < 0 || c->load_shift > kArMaxShift)
+    return gacq::set_error(nullptr, GACQ_ERR_BAD_ARG, "%s: load_shift %d lies outside 0..%d", who, c->load_shift, kArMaxShift);
   if (c->cells < 1 || c->cells > kBrMaxCells)
     return gacq::set_error(nullptr, GACQ_ERR_BAD_ARG, "%s: %d grid cells: need 1..%d", who, c->cells, kBrMaxCells);
   if (c->peaks < 1 || c->peaks > kBrMaxPeaks)

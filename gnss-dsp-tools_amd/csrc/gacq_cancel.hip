@@ -15,9 +15,9 @@
 // Chips are read as bytes from the context's cached tables ("chips:<code>:<prn>", shared with the tracking loops and the simulator)
 // through the cache, reloaded only when a lane's chip index moves: 32 tables of at most 10240 bytes stay resident in L2, consecutive
 // samples mostly share a chip, and no per-tile staging pass is needed.
-// sin / cos: the quarter-turn reduction and polynomials of gacq_simulate.hip in a copy of their own (that file's bits stay what they
-// are).  The int8 output is rint / clamp of the very fp32 values the complex64 output stores.
-// The replica (cancel_sincos_turn, cancel_replica), the device tables CanSat / CanSeg and the host preparation of the segment table are
+// sin / cos: turn_sincos of gacq_turn.h, the one routine gacq_simulate.hip calls, so the replica of a simulated signal is that signal.
+// The int8 output is rint / clamp of the very fp32 values the complex64 output stores.
+// The replica (cancel_replica), the device tables CanSat / CanSeg and the host preparation of the segment table are
 // in gacq_cancelcore.h, which gacq_aprompt.hip shares: its prompts are cancel_project_kernel's amplitudes bit for bit.
 #pragma clang fp contract(off)
 

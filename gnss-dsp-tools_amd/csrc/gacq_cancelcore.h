@@ -3,12 +3,15 @@
 //   theta(j) = (p0 + i F) mod 2^64,  pos(j) = c0 + i Cf,  i = j - s0,   r(j) = w(pos(j)) exp(2 pi i theta(j) / 2^64)
 // and, on the host, the checks of the gacq_cancel_sat / gacq_cancel_seg arrays, their conversion to fixed point, the chip-table lookup
 // and the upload.  One definition of each: what the two files compute for a sample is the same instruction sequence on the same table.
+// The sine / cosine (turn_sincos), the conversions to 2^-64 fixed point (turn_fraction, turn_fixed) and the TMBOC mask are
+// gacq_turn.h's, the very routines of gacq_simcore.h: that is what makes the cancellation of a simulated signal exact.
 // A file includes it under `#pragma clang fp contract(off)`: w cos and w sin are products rounded on their own.
 // `who` is the entry point's name as its messages carry it.
 #pragma once
 
 #include "gacq_common.h"
 #include "gacq_streamhost.h"
+#include "gacq_turn.h"
 
 #include <algorithm>
 #include <cmath>
@@ -23,7 +26,6 @@ constexpr int kCanMaxSegs = 1 << 20;
 constexpr long long kCanMaxN = 1ll << 24;
 constexpr int kCanMaxChips = 10240;             // the tracking loops' limit
 constexpr unsigned kCanMaxGrid = 1u << 16;      // workgroups; a longer call loops
-constexpr unsigned long long kCanTmbocMask = (1ull << 0) | (1ull << 4) | (1ull << 6) | (1ull << 29);
 
 struct CanSat {                                 // device form of a satellite
   const uint8_t* chips;                         // L bytes, 0 / 1
@@ -40,24 +42,6 @@ struct CanSeg {                                 // device form of a segment, 64 
   float ar, ai;                                 // float32(A)
   unsigned sat_touch;                           // satellite index | (the call works on this segment) << 8
 };
-
-// (cos, sin) of 2 pi ph / 2^64
-__device__ __forceinline__ void cancel_sincos_turn(unsigned long long ph, float& c, float& s) {
-  const unsigned u = (unsigned)(ph >> 32) + 0x20000000u;          // + 1/8 turn: the quadrant index rounds to nearest
-  const unsigned q = u >> 30;
-  const float t = (float)((int)(u & 0x3fffffffu) - 0x20000000) * 9.31322574615478515625e-10f;      // quarter turns, [-1/2, 1/2)
-  const float t2 = t * t;
-  float ps = fmaf(t2, -4.602163099e-03f, 7.968021929e-02f);
-  ps = fmaf(ps, t2, -6.459634900e-01f);
-  ps = fmaf(ps, t2, 1.570796371e+00f) * t;
-  float pc = fmaf(t2, 9.036298725e-04f, -2.086007036e-02f);
-  pc = fmaf(pc, t2, 2.536692023e-01f);
-  pc = fmaf(pc, t2, -1.233700514e+00f);
-  pc = fmaf(pc, t2, 1.0f);
-  const float a = (q & 1u) ? ps : pc, b = (q & 1u) ? pc : ps;     // quarter turns: (c, s), (-s, c), (-c, -s), (s, -c)
-  c = __uint_as_float(__float_as_uint(a) ^ ((((q + 1u) >> 1) & 1u) << 31));
-  s = __uint_as_float(__float_as_uint(b) ^ (((q >> 1) & 1u) << 31));
-}
 
 // r = (rr, ri) and w of sample i = u of a segment.  (chip_at, cbit): the chip index whose byte the lane holds
 __device__ __forceinline__ void cancel_replica(const CanSat& s, const CanSeg& g, unsigned u, unsigned& chip_at, unsigned& cbit, float& rr, float& ri,
@@ -83,32 +67,19 @@ __device__ __forceinline__ void cancel_replica(const CanSat& s, const CanSeg& g,
       neg ^= b1;                                                  // w (c1 s1 + c6 s6) = w s1 (c1 +- c6)
       mag = (b1 != b6) ? (float)(0.953463 - 0.301511) : (float)(0.953463 + 0.301511);
     } else {
-      neg ^= ((kCanTmbocMask >> (chip % 33u)) & 1ull) ? b6 : b1;
+      neg ^= ((gacq::kTmbocMask >> (chip % 33u)) & 1ull) ? b6 : b1;
     }
   } else if (s.kind >= 4u) {
     if ((s.kind == 4u) != (b1 == 0u)) mag = 0.0f;
   }
   w = __uint_as_float(__float_as_uint(mag) ^ (neg << 31));
   float c, sn;
-  cancel_sincos_turn(th, c, sn);
+  gacq::turn_sincos(th, c, sn);
   rr = w * c;
   ri = w * sn;
 }
 
 // ---- host ----
-
-// floor(frac(v) 2^64) mod 2^64, in IEEE double operations (as gacq_simulate.hip and tests/simulate_oracle.py have it)
-inline unsigned long long can_turns(double v) {
-  const double t = v - std::floor(v);                               // [0, 1]; 1 only when a tiny negative v rounds up
-  return t >= 1.0 ? 0ull : (unsigned long long)std::floor(std::ldexp(t, 64));
-}
-
-// whole part and floor(fraction 2^64) of v >= 0
-inline void can_fixed(double v, unsigned long long& whole, unsigned long long& frac) {
-  const double w = std::floor(v);
-  whole = (unsigned long long)w;
-  frac = (unsigned long long)std::floor(std::ldexp(v - w, 64));     // v - w is exact and below 1
-}
 
 inline int can_check_rate(const char* who, int K, double fs) {
   if (K < 1 || K > kCanMaxK) return gacq::set_error(nullptr, GACQ_ERR_BAD_ARG, "%s: need 1 <= K <= %d satellites (K %d)", who, kCanMaxK, K);
@@ -201,12 +172,12 @@ int can_table_build(gacq_ctx* ctx, const char* who, const gacq_cancel_sat* sats,
       std::memset(&d, 0, sizeof(d));
       d.s0 = g.s0;
       d.n = (unsigned)g.n;
-      d.F = can_turns(g.carrier_hz / fs);
-      d.p0 = can_turns(g.carrier_phase);
+      d.F = gacq::turn_fraction(g.carrier_hz / fs);
+      d.p0 = gacq::turn_fraction(g.carrier_phase);
       unsigned long long ci, cw;
-      can_fixed(g.code_rate_hz / fs, ci, d.cf_frac);
+      gacq::turn_fixed(g.code_rate_hz / fs, ci, d.cf_frac);
       d.cf_int = (unsigned)ci;
-      can_fixed(g.code_phase, cw, d.frac0);
+      gacq::turn_fixed(g.code_phase, cw, d.frac0);
       d.chip0 = (unsigned)cw;
       d.ar = (float)g.amp_re;
       d.ai = (float)g.amp_im;

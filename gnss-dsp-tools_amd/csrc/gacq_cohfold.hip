@@ -12,14 +12,15 @@
 // Phase: a 64-bit fixed-point fraction of a cycle, exact per sample and reduced before anything becomes fp32.  The host forms
 // S = frac(f_d / fs) 2^128 in two extended-precision pieces, base[d][m] = (j0 + start[d][m]) S / 2^64 mod 2^64 in integer arithmetic
 // and step[d] = S / 2^64 rounded; a lane adds i step[d].  Nothing on the Doppler axis comes from a neighbouring bin.  The top bits
-// pick the nearest quarter turn, the remaining 30 go through polynomials for sin / cos of (pi/2) t, |t| <= 1/2 (1e-7 absolute): the
-// scheme of gacq_corrgrid.hip in a copy of its own, so that file's bits stay what they are.
+// pick the nearest quarter turn, the remaining 30 go through polynomials for sin / cos of (pi/2) t, |t| <= 1/2 (1e-7 absolute):
+// turn_sincos of gacq_turn.h, the scheme of gacq_corrgrid.hip with longer polynomials (that file keeps its own).
 //
 // Every output element is the same chain of operations whatever D, H, the tile, the lanes per sample or the caller's chunking of d
 // are: its bits depend on row d's inputs and W[h] alone.  No atomics, no LDS.
 #pragma clang fp contract(off)
 
 #include "gacq_common.h"
+#include "gacq_turn.h"
 
 #include <cmath>
 #include <cstring>
@@ -34,24 +35,6 @@ constexpr int kFoldBlock = 256;
 constexpr int kFoldMaxM = 128;
 constexpr int kFoldMaxH = 256;
 constexpr int kFoldTileMax = 32;
-
-// (cos, sin) of 2 pi ph / 2^64
-__device__ __forceinline__ void fold_sincos_turn(unsigned long long ph, float& c, float& s) {
-  const unsigned u = (unsigned)(ph >> 32) + 0x20000000u;          // + 1/8 turn: the quadrant index rounds to nearest
-  const unsigned q = u >> 30;
-  const float t = (float)((int)(u & 0x3fffffffu) - 0x20000000) * 9.31322574615478515625e-10f;      // quarter turns, [-1/2, 1/2)
-  const float t2 = t * t;
-  float ps = fmaf(t2, -4.602163099e-03f, 7.968021929e-02f);
-  ps = fmaf(ps, t2, -6.459634900e-01f);
-  ps = fmaf(ps, t2, 1.570796371e+00f) * t;
-  float pc = fmaf(t2, 9.036298725e-04f, -2.086007036e-02f);
-  pc = fmaf(pc, t2, 2.536692023e-01f);
-  pc = fmaf(pc, t2, -1.233700514e+00f);
-  pc = fmaf(pc, t2, 1.0f);
-  const float a = (q & 1u) ? ps : pc, b = (q & 1u) ? pc : ps;     // quarter turns: (c, s), (-s, c), (-c, -s), (s, -c)
-  c = __uint_as_float(__float_as_uint(a) ^ ((((q + 1u) >> 1) & 1u) << 31));
-  s = __uint_as_float(__float_as_uint(b) ^ (((q >> 1) & 1u) << 31));
-}
 
 template <bool WIDE>
 __device__ __forceinline__ float2 fold_load(const void* __restrict__ x, long long j) {
@@ -99,7 +82,7 @@ __global__ __launch_bounds__(kFoldBlock) void cohfold_kernel(const void* __restr
       for (int k = 0; k < IPL; k++) {
         const float2 v = fold_load<WIDE>(x, s0 + ii[k]);
         float c, s;
-        fold_sincos_turn(b0 + ps[k], c, s);
+        turn_sincos(b0 + ps[k], c, s);
         vr[k] = fmaf(v.y, s, v.x * c);                            // x exp(-i phi)
         vi[k] = fmaf(-v.x, s, v.y * c);
       }

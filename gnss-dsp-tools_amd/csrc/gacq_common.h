@@ -165,6 +165,12 @@ __device__ __forceinline__ double2 ld_x(XSrc x, size_t i) {
   const float2 s = reinterpret_cast<const float2*>(x.p)[i];
   return make_double2((double)s.x, (double)s.y);
 }
+// 16 bytes at any address: a byte-aligned copy, for which the compiler emits one wide load
+__device__ __forceinline__ uint4 load16_any(const uint8_t* p) {
+  uint4 v;
+  __builtin_memcpy(&v, p, 16);
+  return v;
+}
 
 int set_error(gacq_ctx* ctx, int code, const char* fmt, ...);
 void ring_destroy(gacq_ctx* ctx);

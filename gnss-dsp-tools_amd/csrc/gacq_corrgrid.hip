@@ -19,6 +19,7 @@
 #pragma clang fp contract(off)
 
 #include "gacq_common.h"
+#include "gacq_turn.h"
 
 #include <cmath>
 #include <cstring>
@@ -34,7 +35,6 @@ constexpr int kCgMaxHyp = 33;                 // D, P <= 33
 constexpr int kTD = 5, kTP = 10;              // accumulator tile: 50 complex fp32 per lane
 constexpr int kCgPadD = (kCgMaxHyp + kTD - 1) / kTD * kTD;
 constexpr int kCgPadP = (kCgMaxHyp + kTP - 1) / kTP * kTP;
-constexpr unsigned long long kTmboc = (1ull << 0) | (1ull << 4) | (1ull << 6) | (1ull << 29);
 
 struct CgSpec {                               // one candidate, device form
   const int8_t* x;                            // interleaved int8 I/Q, sample j at x[2 j], x[2 j + 1]
@@ -46,7 +46,8 @@ struct CgSpec {                               // one candidate, device form
   unsigned long long step[kCgMaxHyp];         // frac((carrier_hz + f_d) / fs) 2^64
 };
 
-// (cos, sin) of 2 pi ph / 2^64
+// (cos, sin) of 2 pi ph / 2^64.  Not gacq_turn.h's turn_sincos: these are shorter polynomials, whose coefficients
+// tests/refine_oracle.py and its goldens restate.
 __device__ __forceinline__ void sincos_turn(unsigned long long ph, float& c, float& s) {
   const unsigned u = (unsigned)(ph >> 32) + 0x20000000u;          // + 1/8 turn: the quadrant index rounds to nearest
   const unsigned q = u >> 30;
@@ -84,7 +85,7 @@ __device__ __forceinline__ float grid_weight(const uint8_t* chips, int L, double
         const double s1 = b1 ? -1.0 : 1.0, s6 = b6 ? -1.0 : 1.0;
         w = w * (float)(0.953463 * s1 + 0.301511 * s6);
       } else {
-        w = ((kTmboc >> (idx % 33)) & 1ull) ? (b6 ? -w : w) : (b1 ? -w : w);
+        w = ((kTmbocMask >> (idx % 33)) & 1ull) ? (b6 ? -w : w) : (b1 ? -w : w);
       }
     } else {
       w = ((kind == 4) == !b1) ? w : 0.0f;

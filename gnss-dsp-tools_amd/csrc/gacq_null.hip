@@ -65,7 +65,7 @@ __global__ __launch_bounds__(kArBlock, 2) void null_cov_kernel(const NlCovArgs a
       for (int g = sub; g < groups; g += wpb) {
         ar_v4i f = {0, 0, 0, 0};
         if (live) {
-          const uint4 lo = ar_load16(pb + 128 * (long long)g), hi = ar_load16(pb + 128 * (long long)g + 16);
+          const uint4 lo = load16_any(pb + 128 * (long long)g), hi = load16_any(pb + 128 * (long long)g + 16);
           f.x = (int)__builtin_amdgcn_perm(lo.y, lo.x, sel);
           f.y = (int)__builtin_amdgcn_perm(lo.w, lo.z, sel);
           f.z = (int)__builtin_amdgcn_perm(hi.y, hi.x, sel);
@@ -139,14 +139,10 @@ __global__ __launch_bounds__(kArBlock) void null_weights_kernel(const NlWgtArgs 
   if (i >= a.nblk) return;
   const int r = lane >> 3, c = lane & 7, M = a.M;
   const bool in = r < M && c < M;
-  // ---- the window sum
+  // ---- the window sum, the loading (gacq_arraycore.h)
   const int* pc = a.C + ((long long)(i >= a.warm ? a.p_off + i - a.W : 0) * 64 + lane) * 2;
-  long long Rre = 0, Rim = 0;
-  for (int j = 0; j < a.W; j++) {
-    const int2 v = *reinterpret_cast<const int2*>(pc + 128 * (long long)j);
-    Rre += v.x;
-    Rim += v.y;
-  }
+  long long Rre, Rim;
+  ar_window_sum(pc, a.W, Rre, Rim);
   const long long b = a.b_first + i;
   const bool owned = b >= a.own_first;
   if (owned && a.cov && in) {
@@ -154,33 +150,16 @@ __global__ __launch_bounds__(kArBlock) void null_weights_kernel(const NlWgtArgs 
     o[0] = Rre;
     o[1] = Rim;
   }
-  // ---- the loading
-  long long t = 0;
-  for (int p = 0; p < M; p++) t += __shfl(Rre, 9 * p, 64);
-  const long long d = (t >> a.shift) + 1;
-  double Are = in ? (double)(Rre + (r == c ? d : 0)) : 0.0, Aim = in ? (double)Rim : 0.0;
+  double Are, Aim;
+  ar_load_diagonal(Rre, Rim, a.shift, M, r, c, Are, Aim);
   double cre = 0.0, cim = 0.0, bre = 0.0, bim = 0.0;                    // c of the lane's column, b of its row
 #pragma unroll
   for (int q = 0; q < kArMaxM; q++) {
     if (c == q && q < M) cre = a.c[2 * q], cim = a.c[2 * q + 1];
     if (r == q && q < M) bre = a.c[2 * q], bim = a.c[2 * q + 1];
   }
-  // ---- elimination: A[r][c] -= m A[k][c], b[r] -= m b[k] with m = A[r][k] / piv, for r > k
-  for (int k = 0; k < M; k++) {
-    const double piv = __shfl(Are, 9 * k, 64);
-    const double lre = __shfl(Are, 8 * r + k, 64), lim = __shfl(Aim, 8 * r + k, 64);
-    const double ure = __shfl(Are, 8 * k + c, 64), uim = __shfl(Aim, 8 * k + c, 64);
-    const double kre = __shfl(bre, 8 * k, 64), kim = __shfl(bim, 8 * k, 64);
-    if (r > k && r < M) {
-      const double mre = lre / piv, mim = lim / piv;
-      if (c > k && c < M) {
-        Are = Are - (mre * ure - mim * uim);
-        Aim = Aim - (mre * uim + mim * ure);
-      }
-      bre = bre - (mre * kre - mim * kim);
-      bim = bim - (mre * kim + mim * kre);
-    }
-  }
+  // ---- elimination, b along with A
+  ar_eliminate<true>(Are, Aim, bre, bim, M, r, c);
   // ---- back substitution: the lane keeps u of its column
   double ucr = 0.0, uci = 0.0;
   for (int k = M - 1; k >= 0; k--) {

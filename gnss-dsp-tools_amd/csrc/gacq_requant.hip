@@ -53,13 +53,6 @@ struct RqPowerArgs {
   int gs, gs_log2;              // lanes per block: a power of two in 2..64, inside one wave, or the whole workgroup of 256
 };
 
-// 16 bytes at any address: a byte-aligned copy, for which the compiler emits one wide load
-__device__ __forceinline__ uint4 rq_load16(const uint8_t* p) {
-  uint4 v;
-  __builtin_memcpy(&v, p, 16);
-  return v;
-}
-
 template <bool IN16>
 __global__ __launch_bounds__(kRqBlock) void requant_power_kernel(const RqPowerArgs a) {
   __shared__ unsigned long long red[kRqBlock / 64];
@@ -73,7 +66,7 @@ __global__ __launch_bounds__(kRqBlock) void requant_power_kernel(const RqPowerAr
       const uint8_t* p = a.in + ((a.pb0 + bl) * a.Lb - a.in_first) * (IN16 ? 4 : 2);
       if (IN16) {
         for (int g = lig; g < a.words; g += a.gs) {
-          const uint4 v = rq_load16(p + 16 * (long long)g);
+          const uint4 v = load16_any(p + 16 * (long long)g);
           const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
           for (int i = 0; i < 4; i++) {
@@ -84,7 +77,7 @@ __global__ __launch_bounds__(kRqBlock) void requant_power_kernel(const RqPowerAr
       } else {
         int s = 0;                                                      // <= 32 words a lane (4 in a group of 64), 2^18 a word
         for (int g = lig; g < a.words; g += a.gs) {
-          const uint4 v = rq_load16(p + 16 * (long long)g);
+          const uint4 v = load16_any(p + 16 * (long long)g);
           s = __builtin_amdgcn_sdot4((int)v.x, (int)v.x, s, false);
           s = __builtin_amdgcn_sdot4((int)v.y, (int)v.y, s, false);
           s = __builtin_amdgcn_sdot4((int)v.z, (int)v.z, s, false);

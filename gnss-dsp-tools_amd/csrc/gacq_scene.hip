@@ -145,7 +145,7 @@ __global__ __launch_bounds__(kScBlock, 4) void scene_kernel(const SceneArgs a) {
         }
         const float amp = __uint_as_float(__float_as_uint(mag) ^ (neg << 31));
         float c, sn;
-        simulate_sincos_turn(th, c, sn);
+        turn_sincos(th, c, sn);
         scene_spread<M, RUN>(g, amp * c, amp * sn, i, vr, vi);
         if (i + 1 < RUN) {
           th += s.F;
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(kScBlock, 4) void scene_kernel(const SceneArgs a) {
         } else {
           const float amp = on ? s.amp : 0.0f;
           float c, sn;
-          simulate_sincos_turn(th, c, sn);
+          turn_sincos(th, c, sn);
           zr = amp * c;
           zi = amp * sn;
         }
@@ -374,8 +374,8 @@ extern "C" int gacq_scene_dev(gacq_ctx* ctx, const gacq_sim_sat* sats, int K, co
     t.gon = e.gate_period ? (unsigned long long)e.gate_on : ~0ull;
     if (e.gate_period) t.g0 = (unsigned long long)((((j0 - e.gate_first) % e.gate_period) + e.gate_period) % e.gate_period);
     if (e.kind == 3) continue;
-    t.F0 = sim_turns(e.f0_hz / fs);
-    const unsigned long long p0 = sim_turns(e.phase);
+    t.F0 = turn_fraction(e.f0_hz / fs);
+    const unsigned long long p0 = turn_fraction(e.phase);
     if (e.kind == 0) {
       t.th0 = p0 + (unsigned long long)j0 * t.F0;
       continue;

@@ -1,10 +1,13 @@
 // What the recording generators share (gacq_simulate.hip, gacq_scene.hip): the device form of a satellite and its conversion from a
-// gacq_sim_sat on the host (fixed point, exact state at j0), the quarter-turn sine / cosine, Philox4x32-10 and the Box-Muller draw.
+// gacq_sim_sat on the host (exact state at j0), Philox4x32-10 and the Box-Muller draw.  The quarter-turn sine / cosine, the
+// conversions to 2^-64 fixed point and the TMBOC mask are gacq_turn.h's, shared with the cancel replica (gacq_cancelcore.h) and
+// gacq_cohfold.hip.
 // Both files compile with `#pragma clang fp contract(off)`; the functions below are inlined into their kernels and keep the
 // operations, and so the bits, gacq_simulate.hip had when they lived there.
 #pragma once
 
 #include "gacq_common.h"
+#include "gacq_turn.h"
 
 #include <cmath>
 #include <cstring>
@@ -15,7 +18,6 @@ namespace gacq {
 constexpr int kSimMaxK = 32;
 constexpr int kSimMaxSym = 1 << 20;
 constexpr long long kSimMaxJ = 1ll << 48;
-constexpr unsigned long long kTmbocMask = (1ull << 0) | (1ull << 4) | (1ull << 6) | (1ull << 29);      // 64 bits: it is shifted by up to 32
 
 struct SimSat {                                 // device form of a satellite, state at j0
   const uint8_t* chips;                         // L bytes, 0 / 1
@@ -27,24 +29,6 @@ struct SimSat {                                 // device form of a satellite, s
   unsigned sub0, sym0;                          // period mod pps and symbol index at j0
   float a0, a1;                                 // amplitude; CBOC: amp (0.953463 + 0.301511) and amp (0.953463 - 0.301511)
 };
-
-// (cos, sin) of 2 pi ph / 2^64
-__device__ __forceinline__ void simulate_sincos_turn(unsigned long long ph, float& c, float& s) {
-  const unsigned u = (unsigned)(ph >> 32) + 0x20000000u;          // + 1/8 turn: the quadrant index rounds to nearest
-  const unsigned q = u >> 30;
-  const float t = (float)((int)(u & 0x3fffffffu) - 0x20000000) * 9.31322574615478515625e-10f;      // quarter turns, [-1/2, 1/2)
-  const float t2 = t * t;
-  float ps = fmaf(t2, -4.602163099e-03f, 7.968021929e-02f);
-  ps = fmaf(ps, t2, -6.459634900e-01f);
-  ps = fmaf(ps, t2, 1.570796371e+00f) * t;
-  float pc = fmaf(t2, 9.036298725e-04f, -2.086007036e-02f);
-  pc = fmaf(pc, t2, 2.536692023e-01f);
-  pc = fmaf(pc, t2, -1.233700514e+00f);
-  pc = fmaf(pc, t2, 1.0f);
-  const float a = (q & 1u) ? ps : pc, b = (q & 1u) ? pc : ps;     // quarter turns: (c, s), (-s, c), (-c, -s), (s, -c)
-  c = __uint_as_float(__float_as_uint(a) ^ ((((q + 1u) >> 1) & 1u) << 31));
-  s = __uint_as_float(__float_as_uint(b) ^ (((q >> 1) & 1u) << 31));
-}
 
 // words 0 and 1 of Philox4x32-10 for the counter (c0, c1, c2, c3)
 __host__ __device__ __forceinline__ void simulate_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned& r0,
@@ -78,22 +62,9 @@ __device__ __forceinline__ void simulate_noise(unsigned long long seed, unsigned
   const float lnu = fmaf(e * 2.98023223876953125e-08f, 1.0f / u, logf(u));
   const float rad = sigma * sqrtf(-2.0f * lnu);
   float c, s;
-  simulate_sincos_turn((unsigned long long)(2u * (r1 >> 8) + 1u) << 39, c, s);
+  turn_sincos((unsigned long long)(2u * (r1 >> 8) + 1u) << 39, c, s);
   re = rad * c;
   im = rad * s;
-}
-
-// floor(frac(v) 2^64) mod 2^64, in IEEE double operations (tests/simulate_oracle.py restates it)
-inline unsigned long long sim_turns(double v) {
-  const double t = v - std::floor(v);                               // [0, 1]; 1 only when a tiny negative v rounds up
-  return t >= 1.0 ? 0ull : (unsigned long long)std::floor(std::ldexp(t, 64));
-}
-
-// whole part and floor(fraction 2^64) of v >= 0
-inline void sim_fixed(double v, unsigned long long& whole, unsigned long long& frac) {
-  const double w = std::floor(v);
-  whole = (unsigned long long)w;
-  frac = (unsigned long long)std::floor(std::ldexp(v - w, 64));     // v - w is exact and below 1
 }
 
 // the checks of a call's range, rate and noise level; ctx may be NULL (the message then goes to gacq_last_error(NULL))
@@ -160,12 +131,12 @@ inline void sim_fill_sats(const gacq_sim_sat* sats, int K, const std::vector<int
     SimSat& t = h[k];
     std::memset(&t, 0, sizeof(t));
     t.chips = d_chips[k];
-    t.F = sim_turns(s.carrier_hz / fs);
-    t.th0 = sim_turns(s.carrier_phase) + (unsigned long long)j0 * t.F;
+    t.F = turn_fraction(s.carrier_hz / fs);
+    t.th0 = turn_fraction(s.carrier_phase) + (unsigned long long)j0 * t.F;
     unsigned long long ci, cw;
-    sim_fixed(s.code_rate_hz / fs, ci, t.cf_frac);
+    turn_fixed(s.code_rate_hz / fs, ci, t.cf_frac);
     t.cf_int = (unsigned)ci;
-    sim_fixed(s.code_phase, cw, t.frac0);
+    turn_fixed(s.code_phase, cw, t.frac0);
     // pos(j0) = c0 + j0 Cf, exact: j0 < 2^48 and Cf < 2^68
     const unsigned __int128 pos = (((unsigned __int128)cw << 64) | t.frac0) + (unsigned __int128)(unsigned long long)j0 * ((((unsigned __int128)ci) << 64) | t.cf_frac);
     t.frac0 = (unsigned long long)pos;

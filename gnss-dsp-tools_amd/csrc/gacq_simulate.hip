@@ -16,12 +16,12 @@
 // ("chips:<code>:<prn>", shared with the tracking loops); consecutive samples mostly hit the same byte, which is reloaded only when
 // the chip index moves.  Symbols are bit-packed in the call's parameter block.
 //
-// sin / cos of the carrier and of the Box-Muller angle: the fixed-point quarter-turn reduction and polynomials of gacq_cohfold.hip
-// in a copy of their own (that file's bits stay what they are).  ln u1 is the accurate logf of u1 rounded to fp32 plus the
+// sin / cos of the carrier and of the Box-Muller angle: the fixed-point quarter-turn reduction and polynomials of gacq_turn.h
+// (turn_sincos, which gacq_cohfold.hip and the cancel replica call too).  ln u1 is the accurate logf of u1 rounded to fp32 plus the
 // first-order term of the rounding, so the radius keeps its relative accuracy where u1 -> 1.
 // The int8 output is rint / clamp of the very fp32 values the complex64 output stores: same operations, same order.
-// The device form of a satellite, its conversion on the host, the sine / cosine, Philox and the Box-Muller draw are in
-// gacq_simcore.h, which gacq_scene.hip shares.
+// The device form of a satellite, its conversion on the host, Philox and the Box-Muller draw are in gacq_simcore.h, which
+// gacq_scene.hip shares.
 #pragma clang fp contract(off)
 
 #include "gacq_simcore.h"
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(kSimBlock) void simulate_kernel(const SimArgs a) {
         }
         const float amp = __uint_as_float(__float_as_uint(mag) ^ (neg << 31));
         float c, sn;
-        simulate_sincos_turn(th, c, sn);
+        turn_sincos(th, c, sn);
         vr[i] = fmaf(amp, c, vr[i]);
         vi[i] = fmaf(amp, sn, vi[i]);
         if (i + 1 < kRun) {

@@ -55,7 +55,7 @@ __device__ __forceinline__ ar_v4i st_fragment(const uint8_t* p, long long s, uns
   if (live) {
     unsigned w[8];
     if (s >= 0) {
-      const uint4 lo = ar_load16(p), hi = ar_load16(p + 16);
+      const uint4 lo = load16_any(p), hi = load16_any(p + 16);
       w[0] = lo.x, w[1] = lo.y, w[2] = lo.z, w[3] = lo.w, w[4] = hi.x, w[5] = hi.y, w[6] = hi.z, w[7] = hi.w;
     } else {
 #pragma unroll

@@ -6,6 +6,7 @@
 #pragma once
 
 #include "gacq_common.h"
+#include "gacq_turn.h"                         // kTmbocMask
 
 #include <cmath>
 #include <vector>
@@ -15,7 +16,6 @@ namespace {
 constexpr int kNcoBits = 10;                  // NT = 1024
 constexpr int kNT = 1 << kNcoBits;
 constexpr double kTwo60 = 1152921504606846976.0;    // NT * 2^50
-constexpr unsigned long long kTmbocMask = (1ull << 0) | (1ull << 4) | (1ull << 6) | (1ull << 29);
 
 enum { kModeFllWide = 0, kModeFllNarrow = 1, kModePll = 2 };
 
@@ -70,7 +70,7 @@ __device__ __forceinline__ double chip_weight(const uint8_t* chips, long L, doub
       const long b6 = (long)floor(fma(12.0 * incr, di, bp60)) & 1;
       const double s1 = b1 ? -1.0 : 1.0, s6 = b6 ? -1.0 : 1.0;
       if (kind == 2) w = w * (0.953463 * s1 + 0.301511 * s6);              // CBOC
-      else w = ((kTmbocMask >> (idx % 33)) & 1ull) ? w * s6 : w * s1;               // TMBOC: u = int(cp % 33)
+      else w = ((gacq::kTmbocMask >> (idx % 33)) & 1ull) ? w * s6 : w * s1;               // TMBOC: u = int(cp % 33)
     } else {
       w = ((kind == 4) == (b1 == 0)) ? w : 0.0;                                     // rz = [1,0] (kind 4) / [0,1] (kind 5)
     }

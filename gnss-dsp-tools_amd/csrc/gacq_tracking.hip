@@ -15,6 +15,7 @@
 // result to fp64 round-off of oracle/tracking_oracle.correlate_many, which forms the phases the same way.
 #include "gacq_common.h"
 #include "gacq_fft64.h"
+#include "gacq_turn.h"
 
 #include <algorithm>
 #include <cmath>
@@ -27,9 +28,6 @@ namespace {
 constexpr int kTrBlock = 256;
 constexpr int kTrPer = 16;
 constexpr int kTrChunk = kTrBlock * kTrPer;
-
-// tmboc_pattern of gnsstools/gps/l1cp.py:202 as a bit mask (bits 0, 4, 6, 29 set)
-constexpr unsigned long long kTmbocMask = (1ull << 0) | (1ull << 4) | (1ull << 6) | (1ull << 29);
 
 struct CorrSpec { const uint8_t* chips; double cp0, bp0, bp60, incr; };
 
