@@ -20,8 +20,8 @@ from . import _native as nat
 from . import codes
 from . import signals as _signals
 
-PEAK_DTYPE = np.dtype([("metric", "<f8"), ("idx", "<i4"), ("d_index", "<i4")])
-RESULT_DTYPE = np.dtype([("metric", "<f8"), ("code_chips", "<f8"), ("doppler_hz", "<f8"), ("idx", "<i4"), ("d_index", "<i4")])      # gacq_result
+PEAK_DTYPE = np.dtype(nat.Peak)
+RESULT_DTYPE = np.dtype(nat.Result)
 
 
 def parse_list_ranges(s, sep='-'):
@@ -230,7 +230,7 @@ class Engine:
     def stage_times(self):
         """{stage name: (total_ms, launches)} from HIP events on the launch stream."""
         out = {}
-        for s in range(7):
+        for s in range(nat.CONSTANTS["GACQ_NSTAGES"]):
             ms, n = ctypes.c_double(), ctypes.c_long()
             nat.check(nat.lib.gacq_get_stage_time(self._ctx, s, ctypes.byref(ms), ctypes.byref(n)), self._ctx)
             out[nat.lib.gacq_stage_name(s).decode()] = (ms.value, n.value)
@@ -644,7 +644,8 @@ class DeviceGroup:
     def set_exchange(self, mode):
         """gacq_group_set_exchange: "host" (records through pinned memory, merged on the host; default) or "rccl" (records stay on
         the devices, one ncclAllGather per chunk over xGMI, tie-safe merge on a member; needs distinct devices)."""
-        self._check(nat.lib.gacq_group_set_exchange(self._g, {"host": 0, "rccl": 1}[mode] if isinstance(mode, str) else int(mode)))
+        modes = {"host": nat.CONSTANTS["GACQ_EXCHANGE_HOST"], "rccl": nat.CONSTANTS["GACQ_EXCHANGE_RCCL"]}
+        self._check(nat.lib.gacq_group_set_exchange(self._g, modes[mode] if isinstance(mode, str) else int(mode)))
 
     def _signal(self, sig, prns):
         key = (sig.name, tuple(prns))

@@ -17,12 +17,12 @@ rms of its first 65536 output samples at gain 1.  --weights-trace writes the qua
 (weight = value / 16384).  Files of unequal length end at the shortest; a recording shorter than W blocks gives no output.  The
 definition is in include/gacq.h; beam k is tests/nulling_oracle.py under c_k."""
 import argparse
-import ctypes
 import re
 import sys
 
 import numpy as np
 
+from . import _native as nat
 from . import arrayfilter, rawfile, streaming
 from .arrayfilter import BLOCK, LOAD_SHIFT, MAX_ANTENNAS, TARGET_RMS, WINDOW, _complex
 from .nulling import auto_window
@@ -31,9 +31,7 @@ from .streaming import first_needed, out_end
 MAX_BEAMS = 16
 
 
-class BeamsCfg(ctypes.Structure):                   # gacq_beams_cfg
-    _fields_ = [("antennas", ctypes.c_int), ("beams", ctypes.c_int), ("block", ctypes.c_int), ("window", ctypes.c_int), ("load_shift", ctypes.c_int),
-                ("c", (ctypes.c_double * 16) * 16)]
+BeamsCfg = nat.struct("gacq_beams_cfg")
 
 
 def make_cfg(M, constraints, block=BLOCK, window=WINDOW, load_shift=LOAD_SHIFT):

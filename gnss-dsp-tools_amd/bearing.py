@@ -36,8 +36,7 @@ STEP, PEAKS, SEP = 5.0, 3, 20.0
 PEAK = np.dtype([("cell", "<i4"), ("zero", "<i4"), ("q", "<f8")])     # a record of gacq_bearing_run_dev
 
 
-class BearingCfg(ctypes.Structure):                 # gacq_bearing_cfg
-    _fields_ = [("antennas", ctypes.c_int), ("load_shift", ctypes.c_int), ("cells", ctypes.c_int), ("peaks", ctypes.c_int), ("cos_sep", ctypes.c_double)]
+BearingCfg = nat.struct("gacq_bearing_cfg")
 
 
 def grid(step_deg, el_min=0.0):

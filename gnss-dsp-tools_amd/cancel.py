@@ -31,12 +31,8 @@ MAX_SEGS = 1 << 20
 MAX_SEG_SAMPLES = 1 << 24
 MAX_INDEX = 1 << 48
 
-SEG_DTYPE = np.dtype([("s0", "i8"), ("n", "i8"), ("carrier_hz", "f8"), ("carrier_phase", "f8"), ("code_rate_hz", "f8"), ("code_phase", "f8"),
-                      ("amp_re", "f8"), ("amp_im", "f8")])                  # gacq_cancel_seg
-
-
-class CancelSat(ctypes.Structure):        # gacq_cancel_sat
-    _fields_ = [("code", ctypes.c_char_p), ("prn", ctypes.c_int), ("kind", ctypes.c_int), ("nseg", ctypes.c_int), ("pad", ctypes.c_int)]
+SEG_DTYPE = np.dtype(nat.struct("gacq_cancel_seg"))
+CancelSat = nat.struct("gacq_cancel_sat")
 
 
 @dataclass(frozen=True)

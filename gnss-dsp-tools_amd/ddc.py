@@ -36,8 +36,7 @@ AUTO_SAMPLES = ingest.AUTO_SAMPLES
 TARGET_RMS = ingest.TARGET_RMS
 
 
-class DdcCfg(ctypes.Structure):                     # gacq_ddc_cfg
-    _fields_ = [("dphase", ctypes.c_uint64), ("decim", ctypes.c_int), ("pad", ctypes.c_int)]
+DdcCfg = nat.struct("gacq_ddc_cfg")
 
 
 def phase_increment(f_shift, fs):

@@ -27,7 +27,7 @@ import numpy as np
 from . import _native as nat
 from . import rawfile, streaming
 
-S8, U8, S16, F32, PACKED = range(5)                 # GACQ_INGEST_*
+S8, U8, S16, F32, PACKED = (nat.CONSTANTS["GACQ_INGEST_" + k] for k in ("S8", "U8", "S16", "F32", "PACKED"))
 CONTAINERS = {"s8": S8, "u8": U8, "s16": S16, "f32": F32}
 PACKED_NAMES = ("1sm", "1ob", "2sm", "2ob", "2tc", "4sm", "4ob", "4tc")
 NAMES = tuple(CONTAINERS) + PACKED_NAMES
@@ -37,9 +37,7 @@ MAX_INDEX = 1 << 48
 TARGET_RMS = 32.0
 
 
-class IngestFmt(ctypes.Structure):                  # gacq_ingest_fmt
-    _fields_ = [("container", ctypes.c_int), ("real", ctypes.c_int), ("bits", ctypes.c_int), ("msb_first", ctypes.c_int),
-                ("conj", ctypes.c_int), ("pad", ctypes.c_int * 3), ("lut", ctypes.c_int8 * 16)]
+IngestFmt = nat.struct("gacq_ingest_fmt")
 
 
 def preset_lut(bits, coding):

@@ -17,7 +17,7 @@ LONG_TRACKERS = {
     "glonass-l2-p": Tracker("glonass.p", 0, 0.5, None, 1.000, 1.0, 1000, glonass=(1246.0, 0.4375, 5.11, 437500)),
 }
 
-STATUS = {**trackloop.STATUS, 3: "code span of a sub-block exceeds the chip window"}
+STATUS = {**trackloop.STATUS, nat.CONSTANTS["GACQ_TRACK_BAD_WINDOW"]: "code span of a sub-block exceeds the chip window"}
 
 
 def long_channel_spec(ch):

@@ -32,9 +32,7 @@ AUTO_SAMPLES = ingest.AUTO_SAMPLES
 TARGET_RMS = ingest.TARGET_RMS
 
 
-class MitigateCfg(ctypes.Structure):                # gacq_mitigate_cfg
-    _fields_ = [("blank_thr", ctypes.c_double), ("ratio", ctypes.c_double), ("hold", ctypes.c_int), ("nfft", ctypes.c_int),
-                ("guard", ctypes.c_int), ("pad", ctypes.c_int)]
+MitigateCfg = nat.struct("gacq_mitigate_cfg")
 
 
 class Config:

@@ -29,7 +29,7 @@ import numpy as np
 from . import _native as nat
 from . import secondary
 
-MAX_R = 20                                   # GACQ_NAV_MAX_R
+MAX_R = nat.CONSTANTS["GACQ_NAV_MAX_R"]
 MAX_STEPS = 1 << 20
 CHUNK_BITS, WARM = 1024, 96
 
@@ -242,10 +242,7 @@ def records_of(periods, name):
 
 # ------------------------------------------------------------------------------------------------ the two device entry points
 
-class VitJob(ctypes.Structure):              # gacq_vit_job
-    _fields_ = [("sym_base", ctypes.c_longlong), ("bit_base", ctypes.c_longlong), ("steps", ctypes.c_int), ("rows", ctypes.c_int),
-                ("cols", ctypes.c_int), ("start_state", ctypes.c_int), ("end_state", ctypes.c_int), ("first_bit", ctypes.c_int),
-                ("nbits", ctypes.c_int), ("g2_inverted", ctypes.c_int)]
+VitJob = nat.struct("gacq_vit_job")
 
 
 def _engine(engine):

@@ -18,17 +18,16 @@ samples at gain 1.  --weights-trace writes the quantised weights of every block,
 of unequal length end at the shortest; a recording shorter than W blocks gives no output.  The definition is in include/gacq.h;
 tests/nulling_oracle.py restates it in numpy."""
 import argparse
-import ctypes
 import sys
 
+from . import _native as nat
 from . import arrayfilter, rawfile, streaming
 # what both array tools share and the block / window algebra, part of this module as before
 from .arrayfilter import AUTO_SAMPLES, BLOCK, LOAD_SHIFT, MAX_ANTENNAS, MAX_BLOCK, MAX_SHIFT, MAX_WINDOW, TARGET_RMS, WINDOW, WQ, _complex, lockstep
 from .streaming import first_needed, out_end, owned_blocks
 
 
-class NullCfg(ctypes.Structure):                    # gacq_null_cfg
-    _fields_ = [("antennas", ctypes.c_int), ("block", ctypes.c_int), ("window", ctypes.c_int), ("load_shift", ctypes.c_int), ("c", ctypes.c_double * 16)]
+NullCfg = nat.struct("gacq_null_cfg")
 
 
 def make_cfg(M, block=BLOCK, window=WINDOW, load_shift=LOAD_SHIFT, constraint=None):

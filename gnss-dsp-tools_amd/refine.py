@@ -84,11 +84,7 @@ class Refined:
     edge: bool
 
 
-class GridSpec(ctypes.Structure):         # gacq_grid_spec
-    _fields_ = [("code", ctypes.c_char_p), ("prn", ctypes.c_int), ("kind", ctypes.c_int), ("n", ctypes.c_int), ("M", ctypes.c_int),
-                ("D", ctypes.c_int), ("P", ctypes.c_int)] + \
-               [(k, ctypes.c_double) for k in ("fs", "carrier_hz", "chip_rate", "ratio", "doppler0", "code0", "df")] + \
-               [("s0", ctypes.c_longlong), ("offsets", ctypes.c_void_p)]
+GridSpec = nat.struct("gacq_grid_spec")
 
 
 def default_grid(c, M=16, D=D_DEFAULT, P=P_DEFAULT, df=None):

@@ -38,9 +38,7 @@ STEP, GAINS, G_MAX = 8, 128, 64.0                   # 2^(1/8) = 0.75 dB a step, 
 TARGET_RMS = {"s8": ingest.TARGET_RMS, "u8": ingest.TARGET_RMS, "s16": 8192.0, "f32": ingest.TARGET_RMS, 1: 2.84, 2: 2.84, 4: 8.44}
 
 
-class RequantCfg(ctypes.Structure):                 # gacq_requant_cfg
-    _fields_ = [("in_bits", ctypes.c_int), ("container", ctypes.c_int), ("bits", ctypes.c_int), ("msb_first", ctypes.c_int),
-                ("block", ctypes.c_int), ("window", ctypes.c_int), ("ngains", ctypes.c_int), ("pad", ctypes.c_int), ("enc", ctypes.c_uint8 * 16)]
+RequantCfg = nat.struct("gacq_requant_cfg")
 
 
 def tables(target_rms, block, window, step=STEP, K=GAINS, g_max=G_MAX):

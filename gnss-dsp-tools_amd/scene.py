@@ -29,10 +29,7 @@ MAX_EMITTERS = 8
 TONE, SAWTOOTH, TRIANGLE, NOISE = 0, 1, 2, 3
 
 
-class SceneEmitter(ctypes.Structure):     # gacq_scene_emitter
-    _fields_ = [("kind", ctypes.c_int), ("pad", ctypes.c_int), ("amp", ctypes.c_double), ("f0_hz", ctypes.c_double), ("f1_hz", ctypes.c_double),
-                ("phase", ctypes.c_double), ("sweep", ctypes.c_longlong), ("gate_period", ctypes.c_longlong), ("gate_on", ctypes.c_longlong),
-                ("gate_first", ctypes.c_longlong)]
+SceneEmitter = nat.struct("gacq_scene_emitter")
 
 
 def _gate(gate):

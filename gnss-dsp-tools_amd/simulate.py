@@ -29,10 +29,7 @@ MAX_SYMBOLS = 1 << 20
 MAX_INDEX = 1 << 48
 
 
-class SimSat(ctypes.Structure):           # gacq_sim_sat
-    _fields_ = [("code", ctypes.c_char_p), ("prn", ctypes.c_int), ("kind", ctypes.c_int), ("periods_per_symbol", ctypes.c_int),
-                ("nsym", ctypes.c_int), ("pad", ctypes.c_int), ("symbols", ctypes.c_void_p)] + \
-               [(k, ctypes.c_double) for k in ("amp", "carrier_hz", "carrier_phase", "code_rate_hz", "code_phase")]
+SimSat = nat.struct("gacq_sim_sat")
 
 
 def tracker(name):

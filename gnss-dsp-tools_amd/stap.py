@@ -20,9 +20,9 @@ S = 10).  --constraint gives the M complex entries of a steering vector, placed 
 quantised weights of every block, M T int32 pairs each, antenna-major (weight = value / 16384).  The last (T - 1) / 2 samples of a
 recording have no output: their taps reach past its end.  The definition is in include/gacq.h; tests/stap_oracle.py restates it."""
 import argparse
-import ctypes
 import sys
 
+from . import _native as nat
 from . import arrayfilter, rawfile, streaming
 # what both array tools share, part of this module as before
 from .arrayfilter import AUTO_SAMPLES, BLOCK, LOAD_SHIFT, MAX_ANTENNAS, MAX_BLOCK, MAX_SHIFT, MAX_WINDOW, TARGET_RMS, WINDOW, WQ, _complex, lockstep
@@ -32,9 +32,7 @@ MAX_TAPS, MAX_WEIGHTS = 15, 56
 TAPS = 5
 
 
-class StapCfg(ctypes.Structure):                    # gacq_stap_cfg
-    _fields_ = [("antennas", ctypes.c_int), ("taps", ctypes.c_int), ("block", ctypes.c_int), ("window", ctypes.c_int), ("load_shift", ctypes.c_int),
-                ("c", ctypes.c_double * 16)]
+StapCfg = nat.struct("gacq_stap_cfg")
 
 
 def make_cfg(M, taps=TAPS, block=BLOCK, window=WINDOW, load_shift=LOAD_SHIFT, constraint=None):

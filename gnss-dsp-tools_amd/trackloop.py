@@ -75,24 +75,12 @@ TRACKERS = {
     "xona-x5p": Tracker("xona.x5p", 0, 0.5, 116.375, 0.001, 1000.0, 1, pll=(0.5, 200), dll=(0.0002, 20), fixed_pll=True),
 }
 
-STATUS = {0: "running", 1: "bad block length", 2: "NCO phase or rate out of range"}
+STATUS = {nat.CONSTANTS["GACQ_TRACK_RUNNING"]: "running", nat.CONSTANTS["GACQ_TRACK_BAD_BLOCK"]: "bad block length",
+          nat.CONSTANTS["GACQ_TRACK_BAD_PHASE"]: "NCO phase or rate out of range"}
 
-
-class TrackSpec(ctypes.Structure):        # gacq_track_spec
-    _fields_ = [("code", ctypes.c_char_p), ("prn", ctypes.c_int), ("kind", ctypes.c_int), ("subs", ctypes.c_int),
-                ("fixed_pll", ctypes.c_int), ("glonass", ctypes.c_int), ("pad", ctypes.c_int)] + \
-               [(k, ctypes.c_double) for k in ("fs", "period", "rate", "ratio", "spacing", "chip_rate", "fll_k_wide", "fll_k_narrow",
-                                               "pll_k1", "pll_k2", "dll_k1", "dll_k2", "coffset", "fm", "code_offset", "doppler",
-                                               "carrier_phase", "dwell_wide", "dwell_narrow")]
-
-
-RECORD_DTYPE = np.dtype([("p_re", "f8"), ("p_im", "f8"), ("carrier_f", "f8"), ("code_f", "f8"), ("early", "f8"), ("prompt", "f8"),
-                         ("late", "f8"), ("code_p", "f8"), ("carrier_p", "f8"), ("block", "i8"), ("code_cyc", "i8"),
-                         ("carrier_cyc", "i8"), ("samp", "i8")])                  # gacq_track_record
-
-STATE_DTYPE = np.dtype([(k, "f8") for k in ("code_p", "code_f", "carrier_p", "carrier_f", "prompt1_re", "prompt1_im", "carrier_e1",
-                                            "code_e1", "coffset_phase")] +
-                       [(k, "i8") for k in ("pos", "block", "samp", "code_cyc", "carrier_cyc")] + [("mode", "i4"), ("status", "i4"), ("last_records", "i4"), ("pad", "i4")])
+TrackSpec = nat.struct("gacq_track_spec")
+RECORD_DTYPE = np.dtype(nat.struct("gacq_track_record"))
+STATE_DTYPE = np.dtype(nat.struct("gacq_track_chstate"))
 
 
 @dataclass

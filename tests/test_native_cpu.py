@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+from gnss_dsp_tools_amd import _cabi as cabi
 from gnss_dsp_tools_amd import _native as nat
 from gnss_dsp_tools_amd import acquire, codes, signals
 from oracle import acq_oracle, codes_oracle
@@ -20,11 +21,159 @@ def test_library_exports_every_declared_symbol():
     hdr = open(os.path.join(ROOT, "include", "gacq.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     declared = set(re.findall(r"\b(gacq_[a-z_0-9]+)\s*\(", hdr))
-    assert len(declared) >= 25
+    assert len(declared) >= 129
     assert declared == set(nat.SYMBOLS), declared ^ set(nat.SYMBOLS)
     lib = ctypes.CDLL(nat.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
+
+
+def _gcc(tmp_path, name, source, run=False):
+    """Compile a C text that includes gacq.h (syntax only, or to a program whose output comes back)"""
+    import subprocess
+    src = tmp_path / (name + ".c")
+    src.write_text(source)
+    cmd = ["gcc", "-std=gnu99", "-I", os.path.join(ROOT, "include"), str(src)] + (["-o", str(tmp_path / name)] if run else ["-fsyntax-only"])
+    build = subprocess.run(cmd, capture_output=True, text=True, timeout=120)
+    assert build.returncode == 0, build.stderr[-4000:]
+    if run:
+        out = subprocess.run([str(tmp_path / name)], capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return out.stdout
+
+
+def test_parsed_prototypes_are_the_compilers(tmp_path):
+    """Every prototype as _cabi read it (return type and parameter types in order, as normalised C text) is compatible with the
+    function gcc sees in the header: a dropped, reordered or misread parameter fails the compile.  The ctypes side follows from that
+    text by the pointer rule, restated here."""
+    assert list(cabi.signatures) == list(cabi.prototypes) == list(nat.SYMBOLS) and len(cabi.signatures) >= 129
+    lines = ['#include "gacq.h"']
+    for name, (ret, params) in cabi.signatures.items():
+        lines.append('_Static_assert(__builtin_types_compatible_p(__typeof__(&%s), %s (*)(%s)), "%s");' % (name, ret, ", ".join(params) or "void", name))
+    _gcc(tmp_path, "prototypes", "\n".join(lines) + "\n")
+
+    def bound(ctype):
+        if ctype == "void":
+            return None
+        if ctype.endswith("*"):
+            return ctypes.c_char_p if ctype == "const char*" else ctypes.c_void_p
+        return cabi.SCALARS[ctype]
+    for name, (ret, params) in cabi.signatures.items():
+        assert nat.SYMBOLS[name] == (bound(ret), [bound(p) for p in params]), name
+        fn = getattr(nat.lib, name)
+        assert fn.restype is bound(ret) and list(fn.argtypes) == [bound(p) for p in params], name
+    assert cabi.signatures["gacq_get_tie_stats"] == ("int", ["gacq_ctx*", "long long*"])           # the array parameter, decayed
+    assert cabi.signatures["gacq_code_name"] == ("const char*", ["int"]) and cabi.signatures["gacq_device_count"] == ("int", [])
+
+
+def test_scalar_type_table_is_the_compilers(tmp_path):
+    """Size, signedness and kind (integer or floating) of every C scalar name of _cabi.SCALARS against the ctypes type it maps to"""
+    body = "".join('  printf("%s|%%d %%d %%d\\n", (int)sizeof(%s), (%s)-1 < 0, (%s)0.5 != 0);\n' % (t, t, t, t) for t in cabi.SCALARS)
+    out = _gcc(tmp_path, "scalars", '#include <stdio.h>\n#include "gacq.h"\nint main(void) {\n' + body + "  return 0;\n}\n", run=True)
+    seen = {}
+    for line in out.splitlines():
+        name, _, nums = line.partition("|")
+        seen[name] = tuple(int(v) for v in nums.split())
+    assert set(seen) == set(cabi.SCALARS)
+    for name, ct in cabi.SCALARS.items():
+        assert seen[name] == (ctypes.sizeof(ct), int(ct(-1).value < 0), int(ct(0.5).value != 0) if ct in (ctypes.c_float, ctypes.c_double) else 0), name
+
+
+def test_every_struct_layout_is_the_compilers(tmp_path):
+    """sizeof of every struct of the header and offsetof / sizeof of every member against the derived ctypes classes: all fields"""
+    assert len(cabi.structs) >= 20
+    body = []
+    for sname, cls in cabi.structs.items():
+        body.append('  printf("%s . %%d\\n", (int)sizeof(%s));\n' % (sname, sname))
+        for fname, _ in cls._fields_:
+            body.append('  printf("%s %s %%d %%d\\n", (int)offsetof(%s, %s), (int)sizeof(((%s*)0)->%s));\n' % (sname, fname, sname, fname, sname, fname))
+    out = _gcc(tmp_path, "layouts", '#include <stdio.h>\n#include <stddef.h>\n#include "gacq.h"\nint main(void) {\n' + "".join(body) + "  return 0;\n}\n", run=True)
+    fields = 0
+    for line in out.splitlines():
+        sname, fname, *nums = line.split()
+        cls = cabi.structs[sname]
+        if fname == ".":
+            assert ctypes.sizeof(cls) == int(nums[0]), sname
+        else:
+            f = getattr(cls, fname)
+            assert (f.offset, f.size) == (int(nums[0]), int(nums[1])), (sname, fname)
+            fields += 1
+    assert fields == sum(len(cls._fields_) for cls in cabi.structs.values()) >= 180
+    # the shapes the rule for members names: arrays of arrays, a const char*, another pointer
+    beams, spec = cabi.structs["gacq_beams_cfg"], cabi.structs["gacq_grid_spec"]
+    assert dict(beams._fields_)["c"] is (ctypes.c_double * 16) * 16
+    assert dict(spec._fields_)["code"] is ctypes.c_char_p and dict(spec._fields_)["offsets"] is ctypes.c_void_p
+    assert nat.struct("gacq_result") is nat.Result is cabi.structs["gacq_result"]
+
+
+@pytest.mark.parametrize("text, quoted", [
+    ("int gacq_f(gacq_nope* p);", "gacq_nope"),                                         # an unknown type
+    ("int gacq_f(short n);", "short"),
+    ("int gacq_f(int n, void (*done)(int));", "gacq_f"),                                 # a function pointer
+    ("typedef struct gacq_s { int a; void (*done)(int); } gacq_s;", "done"),
+    ("typedef struct gacq_s { int a : 3; int b; } gacq_s;", "int a : 3"),                 # a bit-field
+    ("typedef struct gacq_s { int a; union { int b; float c; } u; } gacq_s;", "union"),
+    ("typedef union gacq_u { int b; float c; } gacq_u;", "gacq_u"),
+    ("typedef struct gacq_s { int a; } gacq_s;\nint gacq_f(gacq_s by_value);", "by_value"),
+    ("int gacq_f(int);", "gacq_f"),                                                      # a parameter without a name
+    ("#define GACQ_X (1 << 3)", "GACQ_X"),
+    ("#if 0\nint gacq_f(void);\n#endif", "#if 0"),
+])
+def test_parser_refuses_what_it_does_not_read(text, quoted):
+    with pytest.raises(cabi.CHeaderError) as e:
+        cabi.load(text)
+    assert quoted in str(e.value), str(e.value)
+
+
+def test_parser_reads_the_subset():
+    protos, sigs, structs, consts = cabi.load("""
+        #ifndef X_H
+        #define X_H
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        /* a comment with int gacq_not(void); in it */
+        #define GACQ_A (-3)
+        #define GACQ_B 7   // seven
+        typedef struct gacq_h gacq_h;
+        typedef struct gacq_s { const char* name; double a, b[2]; uint8_t m[2][3]; gacq_h* h; } gacq_s;
+        const char* gacq_f(const gacq_s* s, const void* const* rows, unsigned long long seed, long long out[4], size_t n);
+        void gacq_g(void);
+        #ifdef __cplusplus
+        }
+        #endif
+        #endif
+    """)
+    assert consts == {"GACQ_A": -3, "GACQ_B": 7}
+    assert sigs == {"gacq_f": ("const char*", ["const gacq_s*", "const void* const*", "unsigned long long", "long long*", "size_t"]), "gacq_g": ("void", [])}
+    assert protos == {"gacq_f": (ctypes.c_char_p, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulonglong, ctypes.c_void_p, ctypes.c_size_t]), "gacq_g": (None, [])}
+    assert structs["gacq_s"]._fields_ == [("name", ctypes.c_char_p), ("a", ctypes.c_double), ("b", ctypes.c_double * 2), ("m", (ctypes.c_uint8 * 3) * 2),
+                                          ("h", ctypes.c_void_p)]
+
+
+def test_a_package_without_its_header_says_so(tmp_path):
+    """_cabi.py looks for <package>/../include/gacq.h: a copy of the module in a tree without one fails to import, plainly"""
+    import importlib.util
+    import shutil
+    (tmp_path / "pkg").mkdir()
+    shutil.copy(cabi.__file__, tmp_path / "pkg" / "_cabi.py")
+    spec = importlib.util.spec_from_file_location("_cabi_without_header", tmp_path / "pkg" / "_cabi.py")
+    with pytest.raises(ImportError, match="gacq.h is missing"):
+        spec.loader.exec_module(importlib.util.module_from_spec(spec))
+
+
+def test_constants_and_dtypes_come_from_the_header():
+    from gnss_dsp_tools_amd import cancel, ingest, longtrack, navdata, trackloop
+    assert len(cabi.constants) >= 45 and nat.CONSTANTS is cabi.constants
+    assert nat.ERRORS[0] == "GACQ_OK" and nat.ERRORS[-9] == "GACQ_ERR_UNSUPPORTED" and len(nat.ERRORS) == 10
+    assert (ingest.S8, ingest.U8, ingest.S16, ingest.F32, ingest.PACKED) == (0, 1, 2, 3, 4) and navdata.MAX_R == 20
+    assert sorted(trackloop.STATUS) == [0, 1, 2] and sorted(longtrack.STATUS) == [0, 1, 2, 3]
+    for dt, sname in [(acquire.PEAK_DTYPE, "gacq_peak"), (acquire.RESULT_DTYPE, "gacq_result"), (cancel.SEG_DTYPE, "gacq_cancel_seg"),
+                      (trackloop.RECORD_DTYPE, "gacq_track_record"), (trackloop.STATE_DTYPE, "gacq_track_chstate")]:
+        cls = cabi.structs[sname]
+        assert dt.names == tuple(f for f, _ in cls._fields_) and dt.itemsize == ctypes.sizeof(cls), sname
+        assert [dt.fields[f][1] for f in dt.names] == [getattr(cls, f).offset for f in dt.names], sname
+        assert [dt.fields[f][0] for f in dt.names] == [np.dtype(t) for _, t in cls._fields_], sname
 
 
 def test_struct_layouts_match_header():

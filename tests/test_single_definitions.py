@@ -1,12 +1,15 @@
 """Arithmetic that several tools must share bit for bit has one definition under csrc/, and a copy does not come back: the polynomial
 of the replicas' quarter-turn sine / cosine and the TMBOC chip mask (gacq_turn.h), the trace of the diagonal loading in the lane
-layout 8 r + c of the array weights kernels (gacq_arraycore.h).  Each is recognised by a piece of text that only a definition holds;
-reads sources only, no library and no GPU."""
+layout 8 r + c of the array weights kernels (gacq_arraycore.h).  Each is recognised by a piece of text that only a definition holds.
+The same for the C ABI, whose one definition is include/gacq.h (below).  Reads sources only, no GPU."""
+import ast
 import os
+import re
 
 import pytest
 
-CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "gnss-dsp-tools_amd", "csrc")
+PACKAGE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "gnss-dsp-tools_amd")
+CSRC = os.path.join(PACKAGE, "csrc")
 
 
 @pytest.mark.parametrize("text, home", [
@@ -22,3 +25,61 @@ def test_one_file_holds_it(text, home):
                 if text in f.read():
                     hits.append(name)
     assert hits == [home], (text, hits)
+
+
+# The C ABI has one definition, include/gacq.h: _cabi.py reads it and _native.py binds it.  No other module of the package restates a
+# struct (as a ctypes class or as a numpy record dtype) or a prototype.
+
+def abi_copies(source, struct_members):
+    """What a module's text restates of the header: ctypes.Structure subclasses, .argtypes / .restype assignments, and np.dtype(...)
+    calls on a literal (anything but a name or a call) that spells every member name of a header struct or names one in the comment
+    that ends the statement"""
+    tree, lines, found = ast.parse(source), source.split("\n"), []
+    for node in ast.walk(tree):
+        if isinstance(node, ast.ClassDef) and any("Structure" in ast.unparse(b) or "Union" in ast.unparse(b) for b in node.bases):
+            found.append("class %s" % node.name)
+        if isinstance(node, (ast.Assign, ast.AugAssign, ast.AnnAssign)):
+            for t in (node.targets if isinstance(node, ast.Assign) else [node.target]):
+                if isinstance(t, ast.Attribute) and t.attr in ("argtypes", "restype"):
+                    found.append(ast.unparse(t))
+        if isinstance(node, ast.Call) and ast.unparse(node.func).endswith("dtype") and node.args \
+                and not isinstance(node.args[0], (ast.Name, ast.Attribute, ast.Call, ast.Constant)):
+            words = {c.value for c in ast.walk(node.args[0]) if isinstance(c, ast.Constant) and isinstance(c.value, str)}
+            comment = lines[node.end_lineno - 1][node.end_col_offset:].partition("#")[2]
+            for sname, members in struct_members.items():
+                if set(members) <= words or re.search(r"\b%s\b" % sname, comment):
+                    found.append("dtype of %s" % sname)
+    return found
+
+
+def _struct_members():
+    from gnss_dsp_tools_amd import _cabi
+    return {sname: [f for f, _ in cls._fields_] for sname, cls in _cabi.structs.items()}
+
+
+def test_the_abi_rule_sees_each_kind_of_copy():
+    members = _struct_members()
+    text = '''
+class Peak(ctypes.Structure):
+    _fields_ = []
+lib.gacq_search.argtypes = [ctypes.c_void_p]
+fn.restype = None
+A = np.dtype([("metric", "<f8"), ("idx", "<i4"), ("d_index", "<i4")])
+B = np.dtype([(k, "f8") for k in ("s0", "n")] +
+             [("x", "i4")])        # gacq_cancel_seg
+C = np.dtype([("cell", "<i4"), ("zero", "<i4"), ("q", "<f8")])     # a record of gacq_bearing_run_dev
+D = np.dtype(nat.struct("gacq_peak"))
+E = np.dtype(np.int8)
+'''
+    assert abi_copies(text, members) == ["class Peak", "lib.gacq_search.argtypes", "fn.restype", "dtype of gacq_peak", "dtype of gacq_cancel_seg"]
+
+
+def test_no_module_restates_the_abi():
+    members = _struct_members()
+    seen = 0
+    for name in sorted(os.listdir(PACKAGE)):
+        if name.endswith(".py") and name not in ("_cabi.py", "_native.py"):
+            with open(os.path.join(PACKAGE, name), encoding="utf-8") as f:
+                assert abi_copies(f.read(), members) == [], name
+            seen += 1
+    assert seen >= 39
