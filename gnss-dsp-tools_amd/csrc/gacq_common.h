@@ -37,7 +37,8 @@ constexpr int kTieBit = 0x40000000;
 constexpr int kIdxMask = kTieBit - 1;
 struct TieRow { int ep, d; };                       // row to re-evaluate: ep = epoch * P + item position, d = index into the Doppler grid
 struct TieEp { int ep, slot0, cnt, pad; };          // an ambiguous (epoch, item): its candidate rows are slots [slot0, slot0 + cnt), ascending d
-struct TieRec { double peak, sum; int idx, pad; };  // complex128 result of a re-evaluated row
+namespace f64 { struct RowRec64; }
+using TieRec = f64::RowRec64;                       // complex128 result of a re-evaluated row (gacq_fft64.h)
 struct TieCounters {
   unsigned nrows, neps, pad0, pad1;                 // fill levels of the two lists of the launch in flight (reset by tie_resolve_kernel)
   unsigned long long flagged, rows, overflow, moved;      // cumulative since gacq_create: ambiguous pairs, rows re-evaluated, pairs dropped for lack
@@ -350,13 +351,52 @@ struct Top2 {
   __device__ __forceinline__ void add(float v, int i) {
     if (v > peak) { second = peak; peak = v; idx = i; } else second = fmaxf(second, v);
   }
-  __device__ __forceinline__ void merge(float op, int oi, float os) {
+  // FLAT: the same values without the short-circuit branches (six exec-mask branches per wave reduction otherwise).  Not simply the
+  // one form for everybody: it changes the instruction mix of every caller, and only the matrix-pipe reader was tuned with it.
+  template <bool FLAT = false> __device__ __forceinline__ void merge(float op, int oi, float os) {
     second = fmaxf(fmaxf(second, os), fminf(peak, op));
-    if (op > peak || (op == peak && oi < idx)) { peak = op; idx = oi; }
+    if (FLAT) {
+      const bool take = (op > peak) | ((op == peak) & (oi < idx));
+      peak = take ? op : peak;
+      idx = take ? oi : idx;
+    } else if (op > peak || (op == peak && oi < idx)) {
+      peak = op;
+      idx = oi;
+    }
   }
   // idx with kTieBit set when the runner-up comes within tie_scale of the maximum
   __device__ __forceinline__ int tagged(float tie_scale) const { return idx | ((second >= peak * tie_scale) ? kTieBit : 0); }
 };
+
+// Workgroup-wide reduction of the lanes' (Top2, sum) of one correlation row, for a workgroup of NW waves: the wave step on shuffles
+// (32 down to 1), one LDS slot per wave, then thread 0 merges the waves 1 .. NW - 1 in order.  The result is valid in thread 0, which
+// stores its own record (top.tagged(tie_scale)).  One barrier.  SETS = 2: two slot sets, `set` = 0 / 1 in turn, for a workgroup that
+// reduces row after row with no second barrier -- the sets alternate, so a wave cannot lap the barrier twice.  FLAT: the wave step
+// on Top2::merge<true>.
+template <int NW, int SETS = 1, bool FLAT = false>
+__device__ __forceinline__ void block_reduce_top2(Top2& top, double& sum, int set = 0) {
+  __shared__ float s_peak[SETS][NW], s_second[SETS][NW];
+  __shared__ int s_idx[SETS][NW];
+  __shared__ double s_sum[SETS][NW];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float op = __shfl_down(top.peak, off);
+    const int oi = __shfl_down(top.idx, off);
+    const float o2 = __shfl_down(top.second, off);
+    const double os = __shfl_down(sum, off);
+    top.merge<FLAT>(op, oi, o2);
+    sum += os;
+  }
+  const int t = threadIdx.x, wave = t >> 6;
+  if ((t & 63) == 0) { s_peak[set][wave] = top.peak; s_idx[set][wave] = top.idx; s_second[set][wave] = top.second; s_sum[set][wave] = sum; }
+  __syncthreads();
+  if (t == 0) {
+    for (int w = 1; w < NW; w++) {
+      top.merge(s_peak[set][w], s_idx[set][w], s_second[set][w]);
+      sum += s_sum[set][w];
+    }
+  }
+}
 
 // Combine nparts partial (maximum, idx | tie bit) results of one row -- waves, workgroups or column chunks.  Conservative: a part
 // whose maximum reaches the threshold of the combined maximum counts once, twice if it is ambiguous in itself; two or more make

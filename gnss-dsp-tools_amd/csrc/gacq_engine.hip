@@ -343,31 +343,6 @@ __global__ __launch_bounds__(kBlock) void conj_mul_kernel(const float2* __restri
   }
 }
 
-// Block-wide (peak, first index, sum) reduction shared by K3 and the LDS engine.
-__device__ __forceinline__ void block_reduce_peak(Top2& top, double& sum) {
-  __shared__ float s_peak[kBlock / 64], s_second[kBlock / 64];
-  __shared__ int s_idx[kBlock / 64];
-  __shared__ double s_sum[kBlock / 64];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float op = __shfl_down(top.peak, off);
-    const int oi = __shfl_down(top.idx, off);
-    const float o2 = __shfl_down(top.second, off);
-    const double os = __shfl_down(sum, off);
-    top.merge(op, oi, o2);
-    sum += os;
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { s_peak[wave] = top.peak; s_idx[wave] = top.idx; s_second[wave] = top.second; s_sum[wave] = sum; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kBlock / 64; w++) {
-      top.merge(s_peak[w], s_idx[w], s_second[w]);
-      sum += s_sum[w];
-    }
-  }
-}
-
 // K3: one workgroup per (e,p,d) group: q[k] = sum_b |Y[b][k]| / N, reduced to (max, argmax, sum).
 __global__ __launch_bounds__(kBlock) void mag_peak_kernel(const float2* __restrict__ Y, RowRec* __restrict__ rows,
                                                            long g0, int B, int N, float inv_n, float* __restrict__ q_out, float tie_scale) {
@@ -397,7 +372,7 @@ __global__ __launch_bounds__(kBlock) void mag_peak_kernel(const float2* __restri
       sum += (double)q0;
     }
   }
-  block_reduce_peak(top, sum);
+  block_reduce_top2<kBlock / 64>(top, sum);
   if (threadIdx.x == 0) {
     RowRec r;
     r.peak = top.peak;

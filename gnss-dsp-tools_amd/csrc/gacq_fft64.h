@@ -183,5 +183,142 @@ __device__ __forceinline__ void fft4096(cd (&v)[16], double* lds, cd wa, cd wb, 
   dft16<INV>(v);
 }
 
+// The pass-2 table of fft4096<., TAB2>: w^k, k = 1..15, of the 16 lane classes (lanes 0..15 hold w = W_256^t, conjugated by the caller
+// for an inverse transform), built once per workgroup into s_tw2[15 * 16].  The caller's next barrier publishes it.
+__device__ __forceinline__ void build_tw2(cd* s_tw2, cd w, int t) {
+  if (t < 16) {
+    cd pw[15];
+    make_powers(pw, w);
+#pragma unroll
+    for (int k = 0; k < 15; k++) s_tw2[16 * k + t] = pw[k];
+  }
+}
+
+__device__ __forceinline__ cd ldc(const double2* p) { const double2 v = *p; return cd{v.x, v.y}; }
+__device__ __forceinline__ void stc(double2* p, cd v) { *p = make_double2(v.x, v.y); }
+
+// ---- the complex128 row reduction: (maximum, first argmax, sum) of a correlation row ----------------------------------------------
+// np.argmax returns the first maximum: on equal magnitudes the lower lag wins, in every step below.  The order of the sum is part
+// of the contract (the records of two paths are compared bit for bit): per lane as the caller adds, shfl_down 32 down to 1 (or the
+// DPP tree), then waves 1 to NW - 1 in thread 0; the LDS tree halves from NT / 2 down to 1.
+
+// Result of a re-evaluated / complex128 row (24 bytes; TieLists::recs and the rows buffer of engine 5)
+struct RowRec64 {
+  double peak;
+  double sum;
+  int idx;
+  int pad;
+};
+
+// A lane's, then a wave's, then the workgroup's running result
+struct RowMax {
+  double peak = -1.0, sum = 0.0;
+  int idx = 0x7fffffff;
+  // one magnitude of the lane, lags in any order
+  __device__ __forceinline__ void take(double m, int lag) {
+    if (m > peak || (m == peak && lag < idx)) { peak = m; idx = lag; }
+    sum += m;
+  }
+  // wave step on shuffles: lane 0 of every wave holds the wave's result
+  __device__ __forceinline__ void wave_reduce() {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const double op = __shfl_down(peak, off), os = __shfl_down(sum, off);
+      const int oi = __shfl_down(idx, off);
+      if (op > peak || (op == peak && oi < idx)) { peak = op; idx = oi; }
+      sum += os;
+    }
+  }
+  // cross-wave step of a workgroup of NW waves (one barrier): the row's result, valid in thread 0.  A caller that reduces row after
+  // row needs a barrier of its own before the next call.
+  template <int NW> __device__ __forceinline__ void block_reduce() {
+    __shared__ double s_peak[NW], s_sum[NW];
+    __shared__ int s_idx[NW];
+    const int t = threadIdx.x;
+    if ((t & 63) == 0) { s_peak[t >> 6] = peak; s_idx[t >> 6] = idx; s_sum[t >> 6] = sum; }
+    __syncthreads();
+    if (t == 0) {
+      for (int w = 1; w < NW; w++) {
+        if (s_peak[w] > peak || (s_peak[w] == peak && s_idx[w] < idx)) { peak = s_peak[w]; idx = s_idx[w]; }
+        sum += s_sum[w];
+      }
+    }
+  }
+  __device__ __forceinline__ RowRec64 rec() const { return RowRec64{peak, sum, idx, 0}; }
+};
+
+// wave step on DPP and ballot for a lane t that holds the magnitudes m[k] >= 0 of the lags t + 256 k: maximum first (per lane, then
+// over the wave on DPP), location second (one compare per register against the wave-uniform maximum, lane masks folded on the scalar
+// unit); the result is wave-uniform
+__device__ __forceinline__ RowMax wave_reduce_lags256(const double (&m)[16], int t) {
+  double sum = 0.0, lmax = 0.0;
+#pragma unroll
+  for (int k = 0; k < 16; k++) { sum += m[k]; lmax = fmax(lmax, m[k]); }
+  RowMax a;
+  a.peak = wave_max_pos_f64(lmax);
+#pragma unroll
+  for (int k = 15; k >= 0; k--) {                                 // descending: the last assignment is the smallest k
+    const unsigned long long mk = __builtin_amdgcn_ballot_w64(m[k] == a.peak);
+    if (mk) a.idx = 256 * k + (t & ~63) + (int)__builtin_ctzll(mk);
+  }
+  a.sum = wave_add_f64(sum);
+  return a;
+}
+
+// The whole reduction of the magnitudes val(i), i < N, by a workgroup of nt <= NT threads (a power of two) through an LDS tree; thread
+// 0 writes *dst.  A thread visits i = t, t + nt, ... in ascending order, BATCH values fetched before the first compare: the loads
+// behind val() are independent, the strict-'>' scan is not -- taken one at a time, every value costs a full memory round trip on an
+// otherwise idle chip.  nt is an argument because the re-evaluation kernels of 256 and of 512 threads share one rolled tree loop
+// (nt = blockDim.x); a constant unrolls it.
+template <int NT, int BATCH, class F> __device__ __forceinline__ void tree_reduce_row(int N, F val, RowRec64* dst, int nt = NT) {
+  __shared__ double s_peak[NT], s_sum[NT];
+  __shared__ int s_idx[NT];
+  const int t = threadIdx.x;
+  double peak = -1.0, sum = 0.0;
+  int idx = 0x7fffffff;
+  for (int i0 = t; i0 < N; i0 += BATCH * nt) {
+    double v[BATCH];
+#pragma unroll
+    for (int u = 0; u < BATCH; u++) {
+      const int i = i0 + u * nt;
+      v[u] = i < N ? val(i) : -1.0;
+    }
+#pragma unroll
+    for (int u = 0; u < BATCH; u++) {                                 // ascending i: strict '>' keeps the first maximum
+      const int i = i0 + u * nt;
+      if (i < N) {
+        if (v[u] > peak) { peak = v[u]; idx = i; }
+        sum += v[u];
+      }
+    }
+  }
+  s_peak[t] = peak; s_sum[t] = sum; s_idx[t] = idx;
+  __syncthreads();
+  for (int off = nt / 2; off > 0; off >>= 1) {
+    if (t < off) {
+      const double op = s_peak[t + off];
+      const int oi = s_idx[t + off];
+      if (op > s_peak[t] || (op == s_peak[t] && oi < s_idx[t])) { s_peak[t] = op; s_idx[t] = oi; }
+      s_sum[t] += s_sum[t + off];
+    }
+    __syncthreads();
+  }
+  if (t == 0) *dst = RowRec64{s_peak[0], s_sum[0], s_idx[0], 0};
+}
+
+// K4 on complex128 records: strict-'>' scan over the Doppler bins of one (epoch, item) in order, running best starting at 0
+// (acquire-gps-l1.py:25,36-39); d_of(s): Doppler index of record s.  Nothing above 0: idx = d = -1.
+template <class DOf>
+__device__ __forceinline__ void doppler_scan(const RowRec64* recs, int count, int N, int normalised, DOf d_of, double& best, int& bidx, int& bd) {
+  best = 0.0;
+  bidx = -1;
+  bd = -1;
+  for (int s = 0; s < count; s++) {
+    const RowRec64 r = recs[s];
+    const double m = normalised ? r.peak / (r.sum / (double)N) : r.peak;      // q[idx]/np.mean(q)
+    if (m > best) { best = m; bidx = r.idx; bd = d_of(s); }
+  }
+}
+
 }  // namespace f64
 }  // namespace gacq

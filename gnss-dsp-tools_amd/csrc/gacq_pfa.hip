@@ -313,27 +313,12 @@ __device__ __forceinline__ void add_any(Top2& top, float v, int lag) {
   top.idx = take ? lag : top.idx;
 }
 
-__device__ __forceinline__ void reduce_and_store(Top2 top, double sum, RowRec* __restrict__ partial, long slot, float tie_scale) {
-  __shared__ float s_peak[kBlock / 64], s_second[kBlock / 64];
-  __shared__ int s_idx[kBlock / 64];
-  __shared__ double s_sum[kBlock / 64];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float op = __shfl_down(top.peak, off);
-    const int oi = __shfl_down(top.idx, off);
-    const float o2 = __shfl_down(top.second, off);
-    const double os = __shfl_down(sum, off);
-    top.merge(op, oi, o2);
-    sum += os;
-  }
-  const int t = threadIdx.x;
-  if ((t & 63) == 0) { s_peak[t >> 6] = top.peak; s_idx[t >> 6] = top.idx; s_second[t >> 6] = top.second; s_sum[t >> 6] = sum; }
-  __syncthreads();
-  if (t == 0) {
-    for (int w = 1; w < kBlock / 64; w++) {
-      top.merge(s_peak[w], s_idx[w], s_second[w]);
-      sum += s_sum[w];
-    }
+// the workgroup's (Top2, sum) -> partial[slot] (block_reduce_top2).  ROLLING: the matrix-pipe reader, whose NW waves reduce group after
+// group -- two slot sets in turn (`set` = group parity) and the branch-free wave step
+template <int NW, bool ROLLING = false>
+__device__ __forceinline__ void reduce_and_store(Top2 top, double sum, RowRec* __restrict__ partial, long slot, float tie_scale, int set = 0) {
+  block_reduce_top2<NW, ROLLING ? 2 : 1, ROLLING>(top, sum, set);
+  if (threadIdx.x == 0) {
     RowRec r;
     r.peak = top.peak;
     r.idx = top.tagged(tie_scale);
@@ -422,7 +407,7 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? 1 : 3) void pfa_outer_inverse_k
     top.idx = S::N - 1 - (int)(unsigned)(ks.key & 0xffffffffu);
     sum = (double)sum_f;
   }
-  reduce_and_store(top, sum, partial, g * chunks + chunk, tie_scale);
+  reduce_and_store<kBlock / 64>(top, sum, partial, g * chunks + chunk, tie_scale);
 }
 
 // ---- the same on the matrix pipe ---------------------------------------------------------------------------------------------------
@@ -484,40 +469,6 @@ __device__ __forceinline__ void reader_tile(const v2 (&v)[4], const v2 (&vp)[4],
     // z(u) = A_u + i B_u, z(31 - u) = A_u - i B_u  (plain adds: the accumulator halves are not register pairs)
     const float z1x = aRe[i] - bIm[i], z1y = aIm[i] + bRe[i], z2x = aRe[i] + bIm[i], z2y = aIm[i] - bRe[i];
     out(i, __builtin_fmaf(z1y, z1y, z1x * z1x), __builtin_fmaf(z2y, z2y, z2x * z2x));
-  }
-}
-
-template <int NW>
-__device__ __forceinline__ void reduce_and_store_nw(Top2 top, double sum, RowRec* __restrict__ partial, long slot, float tie_scale, int par) {
-  __shared__ float s_peak[2][NW], s_second[2][NW];
-  __shared__ int s_idx[2][NW];
-  __shared__ double s_sum[2][NW];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float op = __shfl_down(top.peak, off);
-    const int oi = __shfl_down(top.idx, off);
-    const float o2 = __shfl_down(top.second, off);
-    const double os = __shfl_down(sum, off);
-    // Top2::merge without its short-circuit branches (six of them per wave reduction otherwise)
-    top.second = fmaxf(fmaxf(top.second, o2), fminf(top.peak, op));
-    const bool take = (op > top.peak) | ((op == top.peak) & (oi < top.idx));
-    top.peak = take ? op : top.peak;
-    top.idx = take ? oi : top.idx;
-    sum += os;
-  }
-  const int t = threadIdx.x;
-  if ((t & 63) == 0) { s_peak[par][t >> 6] = top.peak; s_idx[par][t >> 6] = top.idx; s_second[par][t >> 6] = top.second; s_sum[par][t >> 6] = sum; }
-  __syncthreads();                                   // the two parities alternate: a wave cannot lap this barrier twice
-  if (t == 0) {
-    for (int w = 1; w < NW; w++) {
-      top.merge(s_peak[par][w], s_idx[par][w], s_second[par][w]);
-      sum += s_sum[par][w];
-    }
-    RowRec r;
-    r.peak = top.peak;
-    r.idx = top.tagged(tie_scale);
-    r.sum = sum;
-    partial[slot] = r;
   }
 }
 
@@ -610,7 +561,7 @@ __global__ __launch_bounds__(PfaReader<M>::RW * 64, MODE == 2 ? 3 : 4) void pfa_
           }
         }
       }
-      reduce_and_store_nw<G::RW>(top, sum, partial, g * G::RCH + chunk, tie_scale, (int)(g & 1));
+      reduce_and_store<G::RW, true>(top, sum, partial, g * G::RCH + chunk, tie_scale, (int)(g & 1));
     }
     return;
   }
@@ -660,7 +611,7 @@ __global__ __launch_bounds__(PfaReader<M>::RW * 64, MODE == 2 ? 3 : 4) void pfa_
     top.peak = (MODE == 0) ? __builtin_amdgcn_sqrtf(p) * inv_n : p;
     top.second = (MODE == 0) ? __builtin_amdgcn_sqrtf(fmaxf(ks.second, 0.f)) * inv_n : ks.second;
     top.idx = S::N - 1 - (int)(unsigned)(ks.key & 0xffffffffu);
-    reduce_and_store_nw<G::RW>(top, (double)sum_f, partial, g * G::RCH + chunk, tie_scale, (int)(g & 1));
+    reduce_and_store<G::RW, true>(top, (double)sum_f, partial, g * G::RCH + chunk, tie_scale, (int)(g & 1));
   }
 }
 

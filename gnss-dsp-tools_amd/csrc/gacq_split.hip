@@ -101,9 +101,6 @@ template <int R, bool TW, bool B1>
 __global__ __launch_bounds__(kBlock, (B1 && R >= 31) ? 3 : 1) void split_outer_inverse_kernel(
     const float2* __restrict__ Z, RowRec* __restrict__ partial, const float2* __restrict__ tw, int M, int B, int chunks, float inv_n,
     float* __restrict__ q_out, int paired, float tie_scale) {
-  __shared__ float s_peak[kBlock / 64], s_second[kBlock / 64];
-  __shared__ int s_idx[kBlock / 64];
-  __shared__ double s_sum[kBlock / 64];
   constexpr bool kNT = B1 || R != 31;              // the multi-block R = 31 kernel (E6B, B3I, E5: 0.94 -> 0.99 ms) is the one case that loses
   const unsigned blk = blockIdx.x;
   const int chunk = (int)(blk % (unsigned)chunks);
@@ -184,23 +181,8 @@ __global__ __launch_bounds__(kBlock, (B1 && R >= 31) ? 3 : 1) void split_outer_i
     }
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float op = __shfl_down(top.peak, off);
-    const int oi = __shfl_down(top.idx, off);
-    const float o2 = __shfl_down(top.second, off);
-    const double os = __shfl_down(sum, off);
-    top.merge(op, oi, o2);
-    sum += os;
-  }
-  const int t = threadIdx.x;
-  if ((t & 63) == 0) { s_peak[t >> 6] = top.peak; s_idx[t >> 6] = top.idx; s_second[t >> 6] = top.second; s_sum[t >> 6] = sum; }
-  __syncthreads();
-  if (t == 0) {
-    for (int w = 1; w < kBlock / 64; w++) {
-      top.merge(s_peak[w], s_idx[w], s_second[w]);
-      sum += s_sum[w];
-    }
+  block_reduce_top2<kBlock / 64>(top, sum);
+  if (threadIdx.x == 0) {
     RowRec r;
     r.peak = top.peak;
     r.idx = top.tagged(tie_scale);

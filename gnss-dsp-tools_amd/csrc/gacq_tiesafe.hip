@@ -29,6 +29,8 @@ constexpr int kMaxPasses = 20;
 struct Radices { int count; unsigned char r[kMaxPasses]; };
 
 using gacq::f64::cd;
+using gacq::f64::ldc;
+using gacq::f64::stc;
 
 // W_N^k = exp(-2 pi i k / N), k < N, evaluated with sincospi on the exactly reduced argument
 __global__ void twiddle64_kernel(double2* __restrict__ w, int N) {
@@ -38,9 +40,6 @@ __global__ void twiddle64_kernel(double2* __restrict__ w, int N) {
   sincospi(-2.0 * (double)k / (double)N, &s, &c);
   w[k] = make_double2(c, s);
 }
-
-__device__ __forceinline__ cd ldc(const double2* p) { const double2 v = *p; return cd{v.x, v.y}; }
-__device__ __forceinline__ void stc(double2* p, cd v) { *p = make_double2(v.x, v.y); }
 
 // 2-, 4- and 8-point DFTs in place, natural order (the powers of two are the bulk of every length)
 template <int R> __device__ __forceinline__ void pow2_dft(cd (&v)[R]) {
@@ -122,44 +121,10 @@ __device__ double2* fft_row(double2* a, double2* b, const double2* __restrict__ 
   return a;
 }
 
-// Workgroup-wide (max, first argmax, sum) of the magnitudes val(i), i < N, visited in ascending order per thread
+// the LDS-tree reduction of a re-evaluated row by a workgroup of either size (256 or kTieThreads), eight loads in flight per lane; the
+// closing barrier lets the work-item loops of the callers reduce row after row
 template <class F> __device__ __forceinline__ void reduce_row(int N, F val, TieRec* dst) {
-  __shared__ double s_peak[kTieThreads], s_sum[kTieThreads];
-  __shared__ int s_idx[kTieThreads];
-  const int t = threadIdx.x;
-  double peak = -1.0, sum = 0.0;
-  int idx = 0x7fffffff;
-  // eight values per lane are fetched before the first compare: the loads behind val() are independent, the strict-'>' scan is not --
-  // taken one at a time, every value costs a full memory round trip on an otherwise idle chip
-  constexpr int kBatch = 8;
-  for (int i0 = t; i0 < N; i0 += kBatch * (int)blockDim.x) {
-    double v[kBatch];
-#pragma unroll
-    for (int u = 0; u < kBatch; u++) {
-      const int i = i0 + u * (int)blockDim.x;
-      v[u] = i < N ? val(i) : -1.0;
-    }
-#pragma unroll
-    for (int u = 0; u < kBatch; u++) {                                 // ascending i: strict '>' keeps the first maximum
-      const int i = i0 + u * (int)blockDim.x;
-      if (i < N) {
-        if (v[u] > peak) { peak = v[u]; idx = i; }
-        sum += v[u];
-      }
-    }
-  }
-  s_peak[t] = peak; s_sum[t] = sum; s_idx[t] = idx;
-  __syncthreads();
-  for (int off = blockDim.x / 2; off > 0; off >>= 1) {
-    if (t < off) {
-      const double op = s_peak[t + off];
-      const int oi = s_idx[t + off];
-      if (op > s_peak[t] || (op == s_peak[t] && oi < s_idx[t])) { s_peak[t] = op; s_idx[t] = oi; }
-      s_sum[t] += s_sum[t + off];
-    }
-    __syncthreads();
-  }
-  if (t == 0) { TieRec r; r.peak = s_peak[0]; r.sum = s_sum[0]; r.idx = s_idx[0]; r.pad = 0; *dst = r; }
+  gacq::f64::tree_reduce_row<kTieThreads, 8>(N, val, dst, (int)blockDim.x);
   __syncthreads();
 }
 
@@ -263,8 +228,6 @@ __global__ __launch_bounds__(256, 1) void tie_recheck4k_kernel(TieLists tl, unsi
                                                                int D, int B) {
   using namespace gacq::f64;
   extern __shared__ __attribute__((aligned(16))) double lds64[];
-  __shared__ double s_peak[4], s_sum[4];
-  __shared__ int s_idx[4];
   const unsigned count = list_count(tl);
   const unsigned nwork = qb ? count * (unsigned)B : count;
   const int t = threadIdx.x;
@@ -325,24 +288,10 @@ __global__ __launch_bounds__(256, 1) void tie_recheck4k_kernel(TieLists tl, unsi
       if (q[k] > peak) { peak = q[k]; idx = t + 256 * k; }
       sum += q[k];
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const double op = __shfl_down(peak, off);
-      const int oi = __shfl_down(idx, off);
-      const double os = __shfl_down(sum, off);
-      if (op > peak || (op == peak && oi < idx)) { peak = op; idx = oi; }
-      sum += os;
-    }
-    if ((t & 63) == 0) { s_peak[t >> 6] = peak; s_idx[t >> 6] = idx; s_sum[t >> 6] = sum; }
-    __syncthreads();
-    if (t == 0) {
-      for (int w2 = 1; w2 < 4; w2++) {
-        if (s_peak[w2] > peak || (s_peak[w2] == peak && s_idx[w2] < idx)) { peak = s_peak[w2]; idx = s_idx[w2]; }
-        sum += s_sum[w2];
-      }
-      TieRec r; r.peak = peak; r.sum = sum; r.idx = idx; r.pad = 0;
-      tl.recs[slot] = r;
-    }
+    RowMax best{peak, sum, idx};
+    best.wave_reduce();
+    best.block_reduce<4>();
+    if (t == 0) tl.recs[slot] = best.rec();
     __syncthreads();
   }
 }
@@ -468,19 +417,10 @@ __global__ __launch_bounds__(256) void tie_resolve_kernel(TieLists tl, gacq_peak
   for (unsigned i = threadIdx.x; i < neps; i += blockDim.x) {
     const TieEp ep = tl.eps[i];
     if (dropped) { out[ep.ep] = fp32_guess[i]; continue; }
-    double best = 0.0;
-    int bidx = -1, bd = -1;
-    for (int s = ep.slot0; s < ep.slot0 + ep.cnt; s++) {
-      const TieRec r = tl.recs[s];
-      const double m = normalised ? r.peak / (r.sum / (double)N) : r.peak;
-      if (m > best) { best = m; bidx = r.idx; bd = tl.rows[s].d; }
-    }
     gacq_peak o;
-    o.metric = best;
-    o.idx = bidx;
-    o.d_index = bd;
+    f64::doppler_scan(tl.recs + ep.slot0, ep.cnt, N, normalised, [&](int s) { return tl.rows[ep.slot0 + s].d; }, o.metric, o.idx, o.d_index);
     const gacq_peak g = fp32_guess[i];
-    if (g.idx != bidx || g.d_index != bd) moved++;
+    if (g.idx != o.idx || g.d_index != o.d_index) moved++;
     out[ep.ep] = o;
   }
   if (moved) atomicAdd(&tl.c->moved, (unsigned long long)moved);

@@ -19,15 +19,11 @@
 #include <cmath>
 
 using namespace gacq;
+using f64::ldc;
+using f64::RowRec64;
+using f64::stc;
 
 namespace {
-
-struct RowRec64 {
-  double peak;
-  double sum;
-  int idx;
-  int pad;
-};
 
 // K1: y = x * tab64[floor((f*i)*1024) & 1023]   (acquire-gps-l1.py:28,30-31, gnsstools/nco.py:6-10), samples widened to fp64
 __global__ __launch_bounds__(kBlock) void mix64_kernel(XSrc x, size_t epoch_stride, double2* __restrict__ y,
@@ -67,50 +63,26 @@ __global__ __launch_bounds__(kBlock) void conj_mul64_kernel(const double2* __res
 // K3: q[k] = sum_b |Y_b[k] / N| in fp64 (the reference's ifft carries the 1/N, then np.absolute, then the sum over blocks)
 __global__ __launch_bounds__(kBlock) void mag_peak64_kernel(const double2* __restrict__ Y, RowRec64* __restrict__ rows, long g0, int B, int N,
                                                              float* __restrict__ q_out) {
-  __shared__ double s_peak[kBlock], s_sum[kBlock];
-  __shared__ int s_idx[kBlock];
   const long gl = blockIdx.x;
   const double2* ys = Y + gl * (long)B * N;
   const double inv_n = 1.0 / (double)N;
-  double peak = -1.0, sum = 0.0;
-  int idx = 0x7fffffff;
-  for (int k = threadIdx.x; k < N; k += kBlock) {
+  f64::tree_reduce_row<kBlock, 1>(N, [&](int k) {
     double q = 0.0;
     for (int b = 0; b < B; b++) {
       const double2 v = ys[(long)b * N + k];
       q += hypot(v.x * inv_n, v.y * inv_n);
     }
     if (q_out) q_out[k] = (float)q;
-    if (q > peak) { peak = q; idx = k; }
-    sum += q;
-  }
-  s_peak[threadIdx.x] = peak; s_sum[threadIdx.x] = sum; s_idx[threadIdx.x] = idx;
-  __syncthreads();
-  for (int off = kBlock / 2; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) {
-      const double op = s_peak[threadIdx.x + off];
-      const int oi = s_idx[threadIdx.x + off];
-      if (op > s_peak[threadIdx.x] || (op == s_peak[threadIdx.x] && oi < s_idx[threadIdx.x])) { s_peak[threadIdx.x] = op; s_idx[threadIdx.x] = oi; }
-      s_sum[threadIdx.x] += s_sum[threadIdx.x + off];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { RowRec64 r; r.peak = s_peak[0]; r.sum = s_sum[0]; r.idx = s_idx[0]; r.pad = 0; rows[g0 + gl] = r; }
+    return q;
+  }, rows + g0 + gl);
 }
 
-// K4: strict-'>' scan over the Doppler bins in order, running best starts at 0 (acquire-gps-l1.py:25,36-39)
+// K4: the Doppler scan of one (epoch, item) per thread
 __global__ void best_doppler64_kernel(const RowRec64* __restrict__ rows, gacq_peak* __restrict__ out, long nep, int D, int N, int normalised) {
   const long ep = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (ep >= nep) return;
-  double best = 0.0;
-  int bidx = -1, bd = -1;
-  for (int d = 0; d < D; d++) {
-    const RowRec64 r = rows[ep * D + d];
-    const double m = normalised ? r.peak / (r.sum / (double)N) : r.peak;      // q[idx]/np.mean(q)
-    if (m > best) { best = m; bidx = r.idx; bd = d; }
-  }
   gacq_peak o;
-  o.metric = best; o.idx = bidx; o.d_index = bd;
+  f64::doppler_scan(rows + ep * D, D, N, normalised, [](int d) { return d; }, o.metric, o.idx, o.d_index);
   out[ep] = o;
 }
 
@@ -130,8 +102,6 @@ __global__ __launch_bounds__(kBlock, 2) void fused4k_c128_kernel(XSrc x, size_t 
                                                                  RowRec64* __restrict__ rows, int E, int P, int D, int pch, int nchunk) {
   using namespace gacq::f64;
   extern __shared__ __attribute__((aligned(16))) double lds64[];
-  __shared__ double s_peak[kBlock / 64], s_sum[kBlock / 64];
-  __shared__ int s_idx[kBlock / 64];
   const int t = threadIdx.x;
   // placement as in lds_fused4k_kernel: all workgroups of an epoch run on XCD e % 8 (the sample block is fetched into one L2)
   const int xcd = blockIdx.x & 7;
@@ -148,12 +118,7 @@ __global__ __launch_bounds__(kBlock, 2) void fused4k_c128_kernel(XSrc x, size_t 
   // pass-2 twiddle powers of the inverse transform, conj(W_256^c)^k for the 16 lane classes c = t & 15: built once per workgroup,
   // read back from a 3.8 KB LDS table in the item loop (the trick of lds_fused4k_kernel)
   __shared__ cd s_tw2[15 * 16];
-  if (t < 16) {
-    cd pw[15];
-    make_powers(pw, conj(wb));                            // lanes 0..15: wb = W_256^t
-#pragma unroll
-    for (int k = 0; k < 15; k++) s_tw2[16 * k + t] = pw[k];
-  }
+  build_tw2(s_tw2, conj(wb), t);                          // lanes 0..15: wb = W_256^t
   cd xr[16];
   {
     const double f = freq[d];
@@ -181,35 +146,15 @@ __global__ __launch_bounds__(kBlock, 2) void fused4k_c128_kernel(XSrc x, size_t 
 #pragma unroll
     for (int j = 0; j < 16; j++) v[j] = v[j] * xr[j];
     fft4096<true, true, GACQ_C128_PRIO>(v, lds64, wa, wb, t, s_tw2 + (t & 15));
-    // (max, first argmax, sum) of the wave's 1024 magnitudes: maximum first (per lane, then over the wave on DPP), location second
-    // (one compare per register against the wave-uniform maximum, lane masks folded on the scalar unit) -- wave_first_max's scheme
-    double m[16], sum = 0.0, lmax = 0.0;
+    double m[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) {                                // lane t holds lags t + 256 k, ascending in k
       const cd r = v[rev16(k)];
       m[k] = sqrt_pos(r.x * r.x + r.y * r.y) * inv_n;             // np.absolute(ifft(...)); 1/N is a power of two
-      sum += m[k];
-      lmax = fmax(lmax, m[k]);
     }
-    double peak = wave_max_pos_f64(lmax);
-    int idx = 0x7fffffff;
-#pragma unroll
-    for (int k = 15; k >= 0; k--) {                               // descending: the last assignment is the smallest k
-      const unsigned long long mk = __builtin_amdgcn_ballot_w64(m[k] == peak);
-      if (mk) idx = 256 * k + (t & ~63) + (int)__builtin_ctzll(mk);
-    }
-    sum = wave_add_f64(sum);
-    if ((t & 63) == 0) { s_peak[t >> 6] = peak; s_idx[t >> 6] = idx; s_sum[t >> 6] = sum; }
-    __syncthreads();      // also orders this item's exchange-2 reads before the next item's exchange-1 writes
-    if (t == 0) {
-      for (int w = 1; w < kBlock / 64; w++) {
-        if (s_peak[w] > peak || (s_peak[w] == peak && s_idx[w] < idx)) { peak = s_peak[w]; idx = s_idx[w]; }
-        sum += s_sum[w];
-      }
-      RowRec64 r;
-      r.peak = peak; r.sum = sum; r.idx = idx; r.pad = 0;
-      rows[(e * P + p) * (long)D + d] = r;
-    }
+    RowMax row = wave_reduce_lags256(m, t);
+    row.block_reduce<kBlock / 64>();      // its barrier also orders this item's exchange-2 reads before the next item's exchange-1 writes
+    if (t == 0) rows[(e * P + p) * (long)D + d] = row.rec();
     // no barrier here: the scratch is rewritten only after the next item's transform, whose first exchange barrier thread 0 reaches
     // after it has finished reading it
   }
@@ -227,8 +172,6 @@ __global__ __launch_bounds__(kBlock, 2) void fused4k_c128_kernel(XSrc x, size_t 
 // plan.  The writer keeps the forward-spectrum row in registers over the items of its chunk (one carrier for all of them) and streams
 // the code-spectrum rows; Z' rows of a pass are ordered (epoch, Doppler bin, item), the records go out in the (epoch, item, Doppler bin)
 // order of the Doppler scan.
-__device__ __forceinline__ f64::cd ldc(const double2* p) { const double2 v = *p; return f64::cd{v.x, v.y}; }
-__device__ __forceinline__ void stc(double2* p, f64::cd v) { *p = make_double2(v.x, v.y); }
 
 // C[p][k] (natural order) -> Cs[p][k1][k2] = C[p][k1 + R k2], k2 < M
 __global__ __launch_bounds__(kBlock) void c128_split_spectra_kernel(const double2* __restrict__ C, double2* __restrict__ Cs, int R, int M) {
@@ -306,12 +249,7 @@ __global__ __launch_bounds__(kBlock, 2) void c128_split_corr_kernel(const double
   // pass-2 twiddle powers W_256^{c k} of the 16 lane classes c = t & 15 from a 3.8 KB LDS table (as in fused4k_c128_kernel): rebuilt
   // per transform they cost the registers the resident forward-spectrum row needs
   __shared__ cd s_tw2[15 * 16];
-  if (t < 16) {
-    cd pw[15];
-    make_powers(pw, wb);
-#pragma unroll
-    for (int k = 0; k < 15; k++) s_tw2[16 * k + t] = pw[k];
-  }
+  build_tw2(s_tw2, wb, t);
   __syncthreads();
   const cd twb = ldc(WN + t * k1);
   cd xs[16];
@@ -346,8 +284,6 @@ __global__ __launch_bounds__(kBlock, 2) void c128_split_reader_kernel(const doub
                                                                       int D, int B, float* __restrict__ q_out) {
   using namespace gacq::f64;
   constexpr int M = kN, N = R * kN;
-  __shared__ double s_peak[kBlock / 64], s_sum[kBlock / 64];
-  __shared__ int s_idx[kBlock / 64];
   const int t = threadIdx.x;
   const long gl = blockIdx.x;                           // ul * P + p
   const long ul = gl / P;
@@ -357,8 +293,7 @@ __global__ __launch_bounds__(kBlock, 2) void c128_split_reader_kernel(const doub
   const int d = (int)(u % D);
   const double inv_n = 1.0 / (double)N;
   const double2* z0 = Z + gl * (long)B * R * M + t;
-  double peak = -1.0, sum = 0.0;
-  int idx = 0x7fffffff;
+  RowMax row;
   for (int j = 0; j < 16; j++) {
     const int n2 = t + 256 * j;
     double acc[R];
@@ -382,29 +317,12 @@ __global__ __launch_bounds__(kBlock, 2) void c128_split_reader_kernel(const doub
     for (int n1 = 0; n1 < R; n1++) {
       const int lag = M * n1 + n2;
       if (q_out) q_out[lag] = (float)acc[n1];
-      if (acc[n1] > peak || (acc[n1] == peak && lag < idx)) { peak = acc[n1]; idx = lag; }      // np.argmax: the first maximum
-      sum += acc[n1];
+      row.take(acc[n1], lag);
     }
   }
-  // (max, first argmax, sum) over the workgroup
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double op = __shfl_down(peak, off), os = __shfl_down(sum, off);
-    const int oi = __shfl_down(idx, off);
-    if (op > peak || (op == peak && oi < idx)) { peak = op; idx = oi; }
-    sum += os;
-  }
-  if ((t & 63) == 0) { s_peak[t >> 6] = peak; s_idx[t >> 6] = idx; s_sum[t >> 6] = sum; }
-  __syncthreads();
-  if (t == 0) {
-    for (int w = 1; w < kBlock / 64; w++) {
-      if (s_peak[w] > peak || (s_peak[w] == peak && s_idx[w] < idx)) { peak = s_peak[w]; idx = s_idx[w]; }
-      sum += s_sum[w];
-    }
-    RowRec64 r;
-    r.peak = peak; r.sum = sum; r.idx = idx; r.pad = 0;
-    rows[(e * P + p) * (long)D + d] = r;
-  }
+  row.wave_reduce();
+  row.block_reduce<kBlock / 64>();
+  if (t == 0) rows[(e * P + p) * (long)D + d] = row.rec();
 }
 
 // ---- N = 31 x M (61380 = 31 x 1980, 30690 = 31 x 990: every 10.23 Mcps script, E6, Xona X5) in complex128 ---------------------------
@@ -489,20 +407,12 @@ __global__ __launch_bounds__(kBlock) void c128_r31_forward_kernel(const double2*
 __global__ __launch_bounds__(kBlock, 2) void c128_r31_reader_kernel(const double2* __restrict__ Z, RowRec64* __restrict__ rows, const double2* __restrict__ WN,
                                                                      long g0, int M, int B, float* __restrict__ q_out) {
   using f64::cd;
-  __shared__ double s_peak[kBlock / 64], s_sum[kBlock / 64];
-  __shared__ int s_idx[kBlock / 64];
   __shared__ double s_acc[31 * kBlock];
   const int t = threadIdx.x;
   const long gl = blockIdx.x;
   const long N = 31L * M;
   const double inv_n = 1.0 / (double)N;
-  double peak = -1.0, sum = 0.0;
-  int idx = 0x7fffffff;
-  auto take = [&](double m, int lag) {
-    if (q_out) q_out[lag] = (float)m;
-    if (m > peak || (m == peak && lag < idx)) { peak = m; idx = lag; }      // np.argmax: the first maximum (lags arrive in any order)
-    sum += m;
-  };
+  f64::RowMax row;
   for (int n2 = t; n2 < M; n2 += kBlock) {
 #pragma unroll
     for (int n1 = 0; n1 < 31; n1++) s_acc[n1 * kBlock + t] = 0.0;
@@ -528,26 +438,16 @@ __global__ __launch_bounds__(kBlock, 2) void c128_r31_reader_kernel(const double
       });
     }
 #pragma unroll
-    for (int n1 = 0; n1 < 31; n1++) take(s_acc[n1 * kBlock + t], M * n1 + n2);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double op = __shfl_down(peak, off), os = __shfl_down(sum, off);
-    const int oi = __shfl_down(idx, off);
-    if (op > peak || (op == peak && oi < idx)) { peak = op; idx = oi; }
-    sum += os;
-  }
-  if ((t & 63) == 0) { s_peak[t >> 6] = peak; s_idx[t >> 6] = idx; s_sum[t >> 6] = sum; }
-  __syncthreads();
-  if (t == 0) {
-    for (int w = 1; w < kBlock / 64; w++) {
-      if (s_peak[w] > peak || (s_peak[w] == peak && s_idx[w] < idx)) { peak = s_peak[w]; idx = s_idx[w]; }
-      sum += s_sum[w];
+    for (int n1 = 0; n1 < 31; n1++) {
+      const double m = s_acc[n1 * kBlock + t];
+      const int lag = M * n1 + n2;
+      if (q_out) q_out[lag] = (float)m;
+      row.take(m, lag);
     }
-    RowRec64 r;
-    r.peak = peak; r.sum = sum; r.idx = idx; r.pad = 0;
-    rows[g0 + gl] = r;
   }
+  row.wave_reduce();
+  row.block_reduce<kBlock / 64>();
+  if (t == 0) rows[g0 + gl] = row.rec();
 }
 
 // ---- N = 4096 with several blocks or carriers (GPS L1 / Xona at --time > 1: the reference CLI's own default is --time 80) in complex128 ----
@@ -589,8 +489,6 @@ __global__ __launch_bounds__(kBlock, 2) void c128_4k_correlate_kernel(const doub
                                                                       int D, int B) {
   using namespace gacq::f64;
   extern __shared__ __attribute__((aligned(16))) double lds64[];
-  __shared__ double s_peak[kBlock / 64], s_sum[kBlock / 64];
-  __shared__ int s_idx[kBlock / 64];
   __shared__ cd s_tw2[15 * 16];
   const int t = threadIdx.x;
   const unsigned xcd = blockIdx.x & 7u, jx = blockIdx.x >> 3;
@@ -600,12 +498,7 @@ __global__ __launch_bounds__(kBlock, 2) void c128_4k_correlate_kernel(const doub
   const long e = u / (unsigned)D;
   const int d = (int)(u % (unsigned)D);
   const cd wa = ldc(tw + t), wb = ldc(tw + 16 * (t & 15));
-  if (t < 16) {
-    cd pw[15];
-    make_powers(pw, conj(wb));                            // pass-2 powers of the inverse transform, as in fused4k_c128_kernel
-#pragma unroll
-    for (int k = 0; k < 15; k++) s_tw2[16 * k + t] = pw[k];
-  }
+  build_tw2(s_tw2, conj(wb), t);                          // pass-2 powers of the inverse transform, as in fused4k_c128_kernel
   cd c[16];
   {
     const double2* cp = C + (long)items[p] * kN + t;
@@ -633,37 +526,9 @@ __global__ __launch_bounds__(kBlock, 2) void c128_4k_correlate_kernel(const doub
       q[k] += sqrt_pos(r.x * r.x + r.y * r.y) * inv_n;                           // np.absolute(ifft(...)), summed over the blocks
     }
   }
-  double sum = 0.0, lmax = 0.0;
-#pragma unroll
-  for (int k = 0; k < 16; k++) { sum += q[k]; lmax = fmax(lmax, q[k]); }
-  double peak = wave_max_pos_f64(lmax);
-  int idx = 0x7fffffff;
-#pragma unroll
-  for (int k = 15; k >= 0; k--) {                                                // descending: the last assignment is the smallest k
-    const unsigned long long mk = __builtin_amdgcn_ballot_w64(q[k] == peak);
-    if (mk) idx = 256 * k + (t & ~63) + (int)__builtin_ctzll(mk);
-  }
-  sum = wave_add_f64(sum);
-  if ((t & 63) == 0) { s_peak[t >> 6] = peak; s_idx[t >> 6] = idx; s_sum[t >> 6] = sum; }
-  __syncthreads();
-  if (t == 0) {
-    for (int w = 1; w < kBlock / 64; w++) {
-      if (s_peak[w] > peak || (s_peak[w] == peak && s_idx[w] < idx)) { peak = s_peak[w]; idx = s_idx[w]; }
-      sum += s_sum[w];
-    }
-    RowRec64 r;
-    r.peak = peak; r.sum = sum; r.idx = idx; r.pad = 0;
-    rows[(e * P + p) * (long)D + d] = r;
-  }
-}
-
-// W_4096^k in fp64 (sincospi on the exactly reduced argument, device-side)
-__global__ void twiddle4096_64_kernel(double2* __restrict__ w) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= 4096) return;
-  double s, c;
-  sincospi(-2.0 * (double)k / 4096.0, &s, &c);
-  w[k] = make_double2(c, s);
+  RowMax row = wave_reduce_lags256(q, t);
+  row.block_reduce<kBlock / 64>();
+  if (t == 0) rows[(e * P + p) * (long)D + d] = row.rec();
 }
 
 int nco_table64(gacq_ctx* ctx, const double2** out) {
@@ -678,20 +543,6 @@ int nco_table64(gacq_ctx* ctx, const double2** out) {
   const int rc = table_cache(ctx, "nco64", h.data(), sizeof(double2) * kNcoTableSize, &p);
   *out = (const double2*)p;
   return rc;
-}
-
-int twiddle64_4096(gacq_ctx* ctx, const double2** out) {
-  auto it = ctx->tables.find("W64_4096");
-  if (it == ctx->tables.end()) {
-    DevBuf b;
-    GACQ_HIP(ctx, hipMalloc(&b.p, sizeof(double2) * 4096));
-    b.cap = sizeof(double2) * 4096;
-    hipLaunchKernelGGL(twiddle4096_64_kernel, dim3(16), dim3(256), 0, ctx->stream, (double2*)b.p);
-    GACQ_HIP(ctx, hipGetLastError());
-    it = ctx->tables.emplace("W64_4096", b).first;
-  }
-  *out = (const double2*)it->second.p;
-  return GACQ_OK;
 }
 
 }  // namespace
@@ -777,8 +628,8 @@ int verify_search(gacq_sig* sig, const SearchPlan& plan, XSrc d_x, size_t nsamp,
   // native radices: no Bluestein); 1 x N, rocFFT's own length-N transform
   const int R = split ? N / f64::kN : r31 ? 31 : 1, M = N / R;
   const double2* tw = nullptr;      // W_4096 of the resident transform (N = 4096) / W_N of the outer stage (split, radix-31)
-  if ((fused || lds4k) && (rc = twiddle64_4096(ctx, &tw)) != GACQ_OK) return rc;
-  if ((split || r31) && ((rc = twiddles64(ctx, N, &tw)) != GACQ_OK || (rc = split_spectra64(sig, R, M, what)) != GACQ_OK)) return rc;
+  if (!rocfft && (rc = twiddles64(ctx, N, &tw)) != GACQ_OK) return rc;
+  if ((split || r31) && (rc = split_spectra64(sig, R, M, what)) != GACQ_OK) return rc;
   const double2* C = (const double2*)(split || r31 ? sig->spectra64_split : sig->spectra64);
   const SplitKernels sk = R == 4 ? split_kernels<4>() : split_kernels<16>();
   const void* lds_kernels[2] = {nullptr, nullptr};      // the form's kernels on the resident transform: 64 KiB of dynamic LDS

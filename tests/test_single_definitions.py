@@ -1,6 +1,9 @@
 """Arithmetic that several tools must share bit for bit has one definition under csrc/, and a copy does not come back: the polynomial
 of the replicas' quarter-turn sine / cosine and the TMBOC chip mask (gacq_turn.h), the trace of the diagonal loading in the lane
-layout 8 r + c of the array weights kernels (gacq_arraycore.h).  Each is recognised by a piece of text that only a definition holds.
+layout 8 r + c of the array weights kernels (gacq_arraycore.h), and the workgroup reduction of a correlation row to (maximum, first
+argmax, sum) -- the fp32 one on Top2 with its runner-up (gacq_common.h), the complex128 one with its record, its per-lane, wave,
+cross-wave and LDS-tree steps, the pass-2 twiddle table and the Doppler scan over the records (gacq_fft64.h), the fp64 twiddle table
+(gacq_tiesafe.hip).  Each is recognised by a piece of text that only a definition holds.
 The same for the C ABI, whose one definition is include/gacq.h (below).  Reads sources only, no GPU."""
 import ast
 import os
@@ -16,6 +19,21 @@ CSRC = os.path.join(PACKAGE, "csrc")
     ("-4.602163099e-03f", "gacq_turn.h"),             # leading sine coefficient of turn_sincos
     ("(1ull << 29)", "gacq_turn.h"),                  # highest bit of the TMBOC mask
     ("__shfl(Rre, 9 * p, 64)", "gacq_arraycore.h"),   # the trace over lanes 9 p
+    # fp32 row reduction: the wave step on shuffles and thread 0's merge of the wave slots
+    ("__shfl_down(top.second, off)", "gacq_common.h"),
+    ("top.merge(s_peak[", "gacq_common.h"),
+    # complex128 row reduction: record, loads / stores, the first-maximum rule per lane (lags in any order), in the shuffle step, in
+    # the cross-wave step and in the LDS tree, the lag of the DPP / ballot step, the pass-2 twiddle table, the Doppler scan
+    ("struct RowRec64 {", "gacq_fft64.h"),
+    ("cd ldc(const double2* p)", "gacq_fft64.h"),
+    ("== peak && lag < idx", "gacq_fft64.h"),
+    ("const double op = __shfl_down(peak, off)", "gacq_fft64.h"),
+    ("&& s_idx[w", "gacq_fft64.h"),
+    ("s_sum[t] += s_sum[t + off]", "gacq_fft64.h"),
+    ("(t & ~63) + (int)__builtin_ctzll(mk)", "gacq_fft64.h"),
+    ("cd pw[15];", "gacq_fft64.h"),
+    ("normalised ? r.peak / (r.sum", "gacq_fft64.h"),
+    ("sincospi(-2.0 * (double)k", "gacq_tiesafe.hip"),  # W_N^k in fp64: one kernel, one table per context and length
 ])
 def test_one_file_holds_it(text, home):
     hits = []

@@ -7,13 +7,20 @@ a pruned template list, a resolved #if).
 
 Kernels are matched by base name and template-argument values (`name<v0,v1,...>`, read from the mangled symbol); --rename gives
 a kernel of the first listing the name it has in the second when the template list itself changed.  Per matched kernel the tool
-prints the instruction count and `same` or `differs`, and exits non-zero on any difference (or when nothing matched).  Kernels in
-only one listing are named and otherwise ignored: a file split is checked with one run per new file.
+prints the instruction count and one of three verdicts:
+    same        body and .amdhsa_kernel block are the same text
+    reordered   the .amdhsa_kernel block is the same and so is the multiset of opcodes: the same instruction mix and resources in
+                another order or with other operands (what moving code into a shared device function typically does to the scheduler)
+    differs     anything else; its diff is printed
+and exits non-zero on any `differs` (or when nothing matched).  Kernels in only one listing are named and otherwise ignored: a file
+split is checked with one run per new file.
 
 What is compared, as text: the kernel's body from its label to its end label, and its .amdhsa_kernel block (register counts, LDS
-bytes, scratch).  Comments are dropped; the kernel's own mangled name (also inside the names of its LDS variables) and the function
+bytes, scratch).  Comments are dropped; the kernel's own mangled name, the enclosing function in the name of a function-local LDS
+variable (the kernel itself or a device function it shares with others: `_ZZ<function>E6s_peak` -> `@L@s_peak`) and the function
 number in local labels are normalised away."""
 import argparse
+import collections
 import difflib
 import re
 import sys
@@ -47,6 +54,21 @@ def kernel_key(sym):
     return "%s<%s>" % (name, ",".join(args))
 
 
+def local_static(m):
+    """`@L@name` for the mangled name of a function-local static (`_ZZ<function encoding>E<len><name>[_<n>]`), whatever the function."""
+    tok = m.group(0)
+    for e in reversed(list(re.finditer(r"E(\d+)", tok))):
+        n = int(e.group(1))
+        name, rest = tok[e.end():e.end() + n], tok[e.end() + n:]
+        if len(name) == n and re.fullmatch(r"[A-Za-z_]\w*", name) and re.fullmatch(r"(_\d*)?", rest):
+            return "@L@" + name
+    return tok
+
+
+def opcodes(body):
+    return collections.Counter(ln.split()[0] for ln in body if not ln.startswith(".") and not ln.endswith(":"))
+
+
 def kernels(path):
     """{key: (body lines, descriptor lines)} of every kernel (a function with an .amdhsa_kernel block) in a -S listing."""
     lines = open(path).read().split("\n")
@@ -66,7 +88,7 @@ def kernels(path):
             ln = re.sub(r"\s*;.*$", "", ln).strip()
             if not ln:
                 continue
-            ln = re.sub(r"\s+", " ", ln.replace(sym[2:], "@K@"))
+            ln = re.sub(r"\s+", " ", re.sub(r"_ZZ\w+", local_static, ln).replace(sym[2:], "@K@"))
             ln = re.sub(r"\.L([A-Za-z_]+)\d+_(\d+)", r".L\1_\2", ln)
             if ln.startswith(".amdhsa_kernel"):
                 where = 1
@@ -95,7 +117,7 @@ def main():
         if old not in ka:
             sys.exit("--rename: no kernel %s in %s (it has: %s)" % (old, a.first, ", ".join(sorted(ka))))
         ka[new] = ka.pop(old)
-    bad = matched = 0
+    bad = matched = moved = 0
     for k in sorted(set(ka) | set(kb)):
         if k not in ka or k not in kb:
             print("%-52s only in %s" % (k, a.second if k in kb else a.first))
@@ -103,15 +125,16 @@ def main():
         matched += 1
         (ba, da), (bb, db) = ka[k], kb[k]
         count = sum(1 for ln in bb if not ln.startswith(".") and not ln.endswith(":"))
-        same = ba == bb and da == db
-        print("%-52s %6d instructions  %s" % (k, count, "same" if same else "differs"))
-        if not same:
+        verdict = "same" if ba == bb and da == db else "reordered" if da == db and opcodes(ba) == opcodes(bb) else "differs"
+        print("%-52s %6d instructions  %s" % (k, count, verdict))
+        moved += verdict == "reordered"
+        if verdict == "differs":
             bad += 1
             diff = list(difflib.unified_diff(ba + da, bb + db, a.first, a.second, lineterm="", n=2))
             print("\n".join(diff[:a.show]))
             if len(diff) > a.show:
                 print("... (%d more lines)" % (len(diff) - a.show))
-    print("%d kernels compared, %d differ" % (matched, bad))
+    print("%d kernels compared, %d reordered, %d differ" % (matched, moved, bad))
     sys.exit(1 if bad or not matched else 0)
 
 
